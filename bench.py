@@ -14,6 +14,21 @@ independent slice of global env ids [rank*P, (rank+1)*P) (weak scaling); the
 data path has no collective. A step = one ``Env.step`` call, through the
 Python API, returning fresh observation/reward/done tensors.
 
+A plain run does only what the headline figure needs: set-up, the clock
+ramp, W warm-up steps, the K timed steps, ``--dump-outputs``, the result
+line. Everything else below (the event-timed and graph-replayed launch
+durations of the roofline block, the CPU baseline) takes runs of its own and
+is behind ``--full``; without it those fields of the line are null.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its
+caller as ``DIR/<name>.npy`` (float32): ``obs`` (the packed (P, A, D)
+observations), ``reward``, ``terminated``, ``truncated`` (flags as 0/1), and
+``states`` (``env.states`` after that step); at most 64 MB in all - beyond
+that, a fixed seeded sample of env rows, whose indices go to
+``env_index.npy`` (float64). Ranks above 0 write ``<name>.rank<r>.npy``. The
+Env's seed and the action tensors' seed are fixed, so two builds given the
+same arguments see the same inputs.
+
 Timing: a GPU clock ramp (``--prewarm`` seconds of back-to-back steps of a
 second, scratch Env of the same shape, before anything of the timed Env
 runs: an idle MI355X starts the first milliseconds of a process at low
@@ -22,7 +37,8 @@ clocks, which at the driver's 20-step setting was the difference between
 barrier + synchronize; K timed steps; synchronize + barrier; the max over
 ranks. value = N*P*K / max time.
 
-roofline (the step kernel): ``launch_us`` = the step kernel's average launch
+roofline (the step kernel; the measured launch durations with ``--full``
+only): ``launch_us`` = the step kernel's average launch
 duration by HIP events on the launch stream (``event_launch_us``): further
 passes of the same K Env.step calls right after the timed region, each behind
 a short device spin so that the events bracket the K launches back to back
@@ -40,8 +56,8 @@ kernel duration of back-to-back launches measures. ``traffic``: HBM bytes per
 launch from the committed rocprofv3 PMC summary for this config (profiles/;
 not measured in this run - the source is named), or null.
 
-cpu_baseline (rank 0 of an N=1 run, after the timed region; null at N>1 unless
---cpu-baseline on): oracle/torch_ref.py - the reference's step
+cpu_baseline (``--full`` only; rank 0 of an N=1 run, after the timed region;
+null at N>1 unless --cpu-baseline on): oracle/torch_ref.py - the reference's step
 restated with its own execution structure in eager PyTorch (pinned bit for
 bit to the reference's golden vectors, tests/test_torch_ref.py) - timed on
 the host CPU with all available cores and with one thread on a bounded
@@ -89,7 +105,17 @@ def parse(argv=None):
     ap.add_argument("--pmc", default=PMC_SUMMARY)
     ap.add_argument("--prewarm", type=float, default=0.3,
                     help="seconds of scratch-Env steps before the timed Env starts")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the event-timed and "
+                         "graph-replayed launch durations (roofline), the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.cpu_baseline == "on" and not a.full:
+        ap.error("--cpu-baseline on needs --full")
+    return a
 
 
 # BASELINE.json configs: (envs, agents, obstacles); configs[4]'s envs are the
@@ -176,6 +202,27 @@ def kernel_time_us(env, actions, n=25, replays=12, per_event=8):
     return sum(per) / len(per), per[len(per) // 2]
 
 
+def event_passes(env, actions, steps, ev0, ev1):
+    """The same K steps again with HIP events on the launch stream around
+    them: the GPU-side time per step of the timed loop (diagnostic; not the
+    value). A short device spin ahead of the start event keeps the queue busy
+    while the host enqueues the first steps, so the region holds the K
+    launches back to back and not the host's start-up gap before the first
+    one (at K = 20 that gap moved launch_us by up to 1.5 us between runs on
+    one box); three such passes, in us per step."""
+    torch.cuda.synchronize()
+    regions = []
+    for rep in range(3):
+        torch.cuda._sleep(SPIN_CYCLES)
+        ev0.record()
+        for i in range(steps):
+            env.step(actions[((2 + rep) * steps + i) % len(actions)])
+        ev1.record()
+        torch.cuda.synchronize()
+        regions.append(ev0.elapsed_time(ev1) * 1e3 / steps)
+    return regions
+
+
 def capture_steps(env, actions, n):
     """A hipGraph of n back-to-back Env.step launches of ``env`` (which must
     allow graph capture; replays repeat the captured re-init draws)."""
@@ -210,6 +257,34 @@ def prewarm(env, actions, seconds):
         torch.cuda.synchronize()
     env.allow_graph_capture = False
     return n
+
+
+DUMP_BUDGET = 64 << 20  # bytes of .npy data per run, all ranks together
+
+
+def dump_outputs(path, out, states, rank, world):
+    """The last timed step's (Observations, reward, terminated, truncated) and
+    the states after it as float32 .npy files; a seeded sample of env rows
+    where the whole would exceed this rank's share of DUMP_BUDGET."""
+    import numpy as np
+    obs, rew, term, trunc = out
+    arrays = {"obs": obs._packed, "reward": rew, "terminated": term, "truncated": trunc,
+              "states": states}
+    P = rew.shape[0]
+    row_bytes = sum(4 * (t.numel() // P) for t in arrays.values())
+    keep = (DUMP_BUDGET // world) // (row_bytes + 8)
+    idx = None
+    if keep < P:
+        idx = np.sort(np.random.RandomState(20251003).choice(P, size=keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    suffix = ".npy" if rank == 0 else f".rank{rank}.npy"
+    if idx is not None:
+        np.save(os.path.join(path, "env_index" + suffix), idx.astype(np.float64))
+        sel = torch.from_numpy(idx).to(rew.device)
+    for name, t in arrays.items():
+        if idx is not None:
+            t = t.index_select(0, sel)
+        np.save(os.path.join(path, name + suffix), t.to(torch.float32).cpu().numpy())
 
 
 def host_cpu_facts():
@@ -363,37 +438,25 @@ def main():
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i in range(a.steps):
+    for i in range(a.steps - 1):
         env.step(actions[i % len(actions)])
+    out = env.step(actions[(a.steps - 1) % len(actions)])  # (kept for --dump-outputs)
     torch.cuda.synchronize()
     barrier()
     dt = time.perf_counter() - t0
     dt = pkg.shard.max_over_ranks(dt, red_dev)
     counters = pkg.shard.sum_over_ranks([env._num_trunc, env._num_col, env._num_tar], red_dev)
     slices = pkg.shard.gather_slices(env._env_offset, P)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, env.states, rank, world)
+    del out
 
-    # the same K steps again with HIP events on the launch stream around
-    # them: the GPU-side time per step of the timed loop (diagnostic; not
-    # the value)
-    # A short device spin ahead of the start event keeps the queue busy while
-    # the host enqueues the first steps, so the region holds the K launches
-    # back to back and not the host's start-up gap before the first one
-    # (at K = 20 that gap moved launch_us by up to 1.5 us between runs on one
-    # box); three such passes, the median.
-    barrier()
-    torch.cuda.synchronize()
-    regions = []
-    for rep in range(3):
-        torch.cuda._sleep(SPIN_CYCLES)
-        ev0.record()
-        for i in range(a.steps):
-            env.step(actions[((2 + rep) * a.steps + i) % len(actions)])
-        ev1.record()
-        torch.cuda.synchronize()
-        regions.append(ev0.elapsed_time(ev1) * 1e3 / a.steps)
-    region_us = sorted(regions)[1]
-
-    kern_us, kern_med = kernel_time_us(kenv, actions)
+    regions = region_us = kern_us = kern_med = achieved = None
+    if a.full:
+        barrier()
+        regions = event_passes(env, actions, a.steps, ev0, ev1)
+        region_us = sorted(regions)[1]
+        kern_us, kern_med = kernel_time_us(kenv, actions)
     del kenv
     per_env = alg_bytes_per_env(A, O)
     launch_bytes = per_env * P
@@ -404,14 +467,15 @@ def main():
     # included: a lower bound on the kernel's own rate). The graph-replay
     # figure is kept beside them.
     step_us = dt * 1e6 / a.steps
-    achieved = launch_bytes / (region_us * 1e-6) / 1e9
+    if a.full:
+        achieved = launch_bytes / (region_us * 1e-6) / 1e9
     timed_frac = launch_bytes / (step_us * 1e-6) / 1e9 / HBM_PEAK_GBS
     traffic, traffic_src = load_traffic(a.pmc, f"P{P}_A{A}_O{O}")
 
     cpu = None
     # (the CPU baseline belongs to the N=1 line; --cpu-baseline on forces it)
     want_cpu = a.cpu_baseline == "on" or (a.cpu_baseline == "auto" and world == 1)
-    if rank == 0 and want_cpu:
+    if rank == 0 and want_cpu and a.full:
         cpu = cpu_baseline(P, A, O, a.cpu_seconds, device)
 
     if rank == 0:
@@ -435,11 +499,13 @@ def main():
                        "global_envs": world * P, "episode_len": 200,
                        "parallelism": f"independent env slices x{world}, no collective"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                         "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK_GBS if a.full else None,
                          "traffic": traffic, "traffic_source": traffic_src,
                          "launch_us": region_us,
                          "launch_us_source": "HIP events on the launch stream, K back-to-back "
-                                             "Env.step launches after the timed region (median of 3)",
+                                             "Env.step launches after the timed region (median of 3)"
+                                             if a.full else "not measured (--full)",
                          "timed_region_frac": timed_frac,
                          "timed_region_launch_us": step_us,
                          "event_launch_us": region_us,
@@ -451,7 +517,9 @@ def main():
             "cpu_baseline": cpu,
             **({} if cpu is not None else
                {"cpu_baseline_note": "off" if a.cpu_baseline == "off"
+                else "not measured (--full)" if not a.full
                 else "measured on rank 0 of the N=1 run only"}),
+            "full": a.full,
             "prewarm": {"seconds": a.prewarm, "scratch_env_steps": prewarm_steps},
             "episode_counters": counters,
             "ranks": [{"rank": r, "env_offset": off, "envs": n} for r, off, n in slices],

@@ -29,15 +29,15 @@ on() { [ "${!1:-1}" = 1 ]; }
 on TESTS && step pytest_gpu 600 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-method thread
 on SMOKE && step smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
 if on BENCH; then
-  step bench_drv1 200 python bench.py --steps 20 --warmup 5 --cpu-baseline off
-  step bench_drv2 200 python bench.py --steps 20 --warmup 5 --cpu-baseline off
-  step bench_500 300 python bench.py --steps 500 --warmup 50
+  step bench_drv1 200 python bench.py --full --steps 20 --warmup 5 --cpu-baseline off
+  step bench_drv2 200 python bench.py --full --steps 20 --warmup 5 --cpu-baseline off
+  step bench_500 300 python bench.py --full --steps 500 --warmup 50
 fi
 if on PROF; then
   step rocprof 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o run \
-      -- python bench.py --steps 200 --warmup 20 --cpu-baseline off
+      -- python bench.py --full --steps 200 --warmup 20 --cpu-baseline off
   step rocprof_c4 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c4_$TAG -o run \
-      -- python bench.py --envs 16384 --steps 200 --warmup 20 --cpu-baseline off
+      -- python bench.py --full --envs 16384 --steps 200 --warmup 20 --cpu-baseline off
   step rocprof_2m 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_2m_$TAG -o run \
       -- python scripts/pmc_run.py 2097152x3x3 300
   step rocprof_c3 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c3_$TAG -o run \

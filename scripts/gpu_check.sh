@@ -23,10 +23,10 @@ step() {  # name timeout cmd...
 rocminfo 2>/dev/null | grep -m2 -E "Marketing Name|gfx" > "$OUT/device.txt" || true
 step pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ${PYTEST_ARGS:-}
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python bench.py --steps 500 --warmup 50
-step bench_drv 300 python bench.py --steps 20 --warmup 5 --cpu-baseline off
+step bench 600 python bench.py --full --steps 500 --warmup 50
+step bench_drv 300 python bench.py --full --steps 20 --warmup 5 --cpu-baseline off
 if [ "${PROFILE:-1}" = 1 ]; then
   step rocprof_stats 600 rocprofv3 --kernel-trace --stats --output-format csv \
-      -d "$OUT/prof_$TAG" -o run -- python bench.py --steps 200 --warmup 20 --cpu-baseline off
+      -d "$OUT/prof_$TAG" -o run -- python bench.py --full --steps 200 --warmup 20 --cpu-baseline off
 fi
 echo done

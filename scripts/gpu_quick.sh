@@ -17,9 +17,9 @@ step() {
 [ "${TESTS:-1}" = 1 ] && step pytest_gpu 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread ${K:+-k "$K"}
 [ "${SMOKE:-1}" = 1 ] && step smoke 200 python -c "import __graft_entry__ as g; g.smoke()"
 [ "${BENCH:-1}" = 1 ] && {
-  step bench_drv1 200 python bench.py --steps 20 --warmup 5 --cpu-baseline off
-  step bench_drv2 200 python bench.py --steps 20 --warmup 5 --cpu-baseline off
-  step bench_500 200 python bench.py --steps 500 --warmup 50 ${CPUB:---cpu-baseline off}
+  step bench_drv1 200 python bench.py --full --steps 20 --warmup 5 --cpu-baseline off
+  step bench_drv2 200 python bench.py --full --steps 20 --warmup 5 --cpu-baseline off
+  step bench_500 200 python bench.py --full --steps 500 --warmup 50 ${CPUB:---cpu-baseline off}
 }
 [ "${GLOO2:-0}" = 1 ] && MARLNAV_BENCH_BACKEND=gloo step bench_gloo2 300 python bench.py --gpus 2 --steps 20 --warmup 5
 exit 0
