@@ -83,16 +83,9 @@ __device__ __forceinline__ void out_st4(float *p, float4 v)
 // but 2x3x3 (configs[0]) 2.85 -> 3.24 / 2.75 -> 2.91: the threshold is 64 KB.
 // marlnav_step / marlnav_observe set kWriteThroughFlag in
 // MarlnavParams.flags; `wt` in the kernels is that bit.
-#ifndef MARLNAV_CPOL
-#define MARLNAV_CPOL 17  // SC0 | SC1
-#endif
-constexpr int kCpolOut = MARLNAV_CPOL < 0 ? 0 : MARLNAV_CPOL;
-constexpr bool kWtOut = MARLNAV_CPOL >= 0;
+constexpr int kCpolOut = 17;  // SC0 | SC1
 constexpr uint32_t kWriteThroughFlag = 1u << 29;  // internal MarlnavParams.flags bit
-#ifndef MARLNAV_WT_MIN_KB
-#define MARLNAV_WT_MIN_KB 64
-#endif
-constexpr int64_t kWriteThroughMinBytes = (int64_t)MARLNAV_WT_MIN_KB << 10;
+constexpr int64_t kWriteThroughMinBytes = (int64_t)64 << 10;
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef int v2i_t __attribute__((ext_vector_type(2)));
 
@@ -159,8 +152,7 @@ __device__ __forceinline__ void out_st2(float *p, float2 v)
 // (CoordRange / tile_coords_ok), which implies every per-pair guard, so
 // there the guards are dead code. The generic wave kernel, which would have
 // to evaluate the guards per pair, was measured slower with them and runs
-// IEEE-only (kGuardedFast).
-constexpr bool kGuardedFast = false;
+// IEEE-only.
 // Internal MarlnavParams.flags bit set by marlnav_step when every reward
 // parameter lies inside the short division sequences' guards
 // (terms_fast_params): the observe_row_own reward terms then use them in
@@ -250,7 +242,6 @@ template <bool FAST = false>
 __device__ __forceinline__ float pair_dist(float ox, float oy, float px, float py, bool &ok)
 {
     const float dx = px - ox, dy = py - oy;
-    if (FAST && (MARLNAV_AB & 64)) return dx + dy;  // timing only: trivial pair math
     if constexpr (FAST)
         return sqrt_fast(__builtin_fmaf(dy, dy, dx * dx), ok);
     else
@@ -332,33 +323,12 @@ __device__ __forceinline__ void div2_fast(float x, float y, float den, float *qx
 // correctly rounded, is restated from an exhaustive measurement of it on the
 // only r that branch produces (k * 2^-25, tests/golden/vsqrt_r_grid.npz), so
 // kernel and oracle bearings agree bit for bit (tests/golden/acos_dev_check.py
-// checks every fp32 in [-1, 1]). MARLNAV_ACOS_CR_SQRT (A/B builds): the same
-// sequence with the correctly rounded sqrt (sqrt_fast) - five more VALU per
-// bearing, measured +0.24 us at 16384x3x3 and +0.32 us at 4096x16x32.
-#ifndef MARLNAV_ACOS_CR_SQRT
-#define MARLNAV_ACOS_CR_SQRT 0
-#endif
+// checks every fp32 in [-1, 1]). The same sequence with the correctly rounded
+// sqrt (sqrt_fast) took five more VALU per bearing and measured +0.24 us at
+// 16384x3x3 and +0.32 us at 4096x16x32.
 __device__ __forceinline__ float acos_k(float x)
 {
-    if (!MARLNAV_ACOS_CR_SQRT) return acosf(x);
-    const float ax = fabsf(x);
-    const float rt = __builtin_fmaf(ax, -0.5f, 0.5f);
-    const float x2 = x * x;
-    const bool big = ax > 0.5f;
-    const float r = big ? rt : x2;
-    float p = __builtin_fmaf(__uint_as_float(0x3d1c21a7u), r, __uint_as_float(0x3c5fc5dau));
-    p = __builtin_fmaf(r, p, __uint_as_float(0x3d034c3cu));
-    p = __builtin_fmaf(r, p, __uint_as_float(0x3d3641b1u));
-    p = __builtin_fmaf(r, p, __uint_as_float(0x3d999bc8u));
-    p = __builtin_fmaf(r, p, __uint_as_float(0x3e2aaaacu));
-    const float u = r * p;
-    bool unused = true;
-    const float sq = sqrt_fast(r, unused);
-    const float s2 = __builtin_fmaf(sq, u, sq);
-    const float zt = s2 + s2;
-    const float ztn = __uint_as_float(0x40490fdbu) - zt;                      // pi - 2 asin(sqrt r)
-    const float zs = __uint_as_float(0x3fc90fdbu) - __builtin_fmaf(x, u, x);  // pi/2 - asin(x)
-    return big ? (x < 0.0f ? ztn : zt) : zs;
+    return acosf(x);
 }
 
 // The bearing of a normalised difference (nx, ny) seen from heading (dirx,
@@ -385,7 +355,6 @@ __device__ __forceinline__ float pair_angle(float ox, float oy, float px, float 
                                             bool &ok)
 {
     const float dx = px - ox, dy = py - oy;
-    if (FAST && (MARLNAV_AB & 64)) return dx * dirx + dist;  // timing only: trivial pair math
     // F.normalize's clamp_min(1e-12). FAST (finite, non-negative dist): one
     // v_med3 instead of a canonicalize + v_max
     const float den = FAST ? __builtin_amdgcn_fmed3f(dist, 1e-12f, __builtin_inff())
@@ -416,6 +385,10 @@ __device__ __forceinline__ float pair_angle(float ox, float oy, float px, float 
 // clang vectors (W = 2, 4, 6) compiled to dependent packed instructions
 // back to back, each pair of them separated by an s_nop, and measured
 // slower (profiles/r06_pair_forms_widths.txt, r06_ab_packed_widths.txt).
+// Used by the env-block kernel's coordinate-checked observation
+// (observe_row_own): block_kernel<3,3> at 65536x3x3 578.6 -> 497.6 VALU per
+// wave, observe phase 1210 -> 1149 quad-cycles (profiles/r06_valu_census.txt).
+// The pair-split kernel keeps one pair per instruction (split_pairs).
 typedef float f2_t __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ f2_t pk_fma(f2_t a, f2_t b, f2_t c)
@@ -524,12 +497,7 @@ __device__ __forceinline__ void pairs_fast(float ox, float oy, float dirx, float
 __device__ __forceinline__ void sincos_k(float th, float *s_out, float *c_out)
 {
     const double x = (double)th;
-    if (MARLNAV_AB & 128) {  // timing only: no sin/cos
-        *s_out = th;
-        *c_out = 1.0f - th;
-        return;
-    }
-    if (!(MARLNAV_AB & 32) && __ballot(!(fabsf(th) < 0.78f)) == 0ull) {
+    if (__ballot(!(fabsf(th) < 0.78f)) == 0ull) {
         const double z = x * x;
         double ps = __builtin_fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
         ps = __builtin_fma(z, ps, 2.75573137070700676789e-06);
@@ -641,7 +609,7 @@ __device__ __forceinline__ void native_block(uint64_t seed, uint32_t blk, uint64
 {
     r0 = (uint32_t)gid;
     r1 = (uint32_t)s ^ ((uint32_t)(gid >> 32) * 0x85EBCA77u);
-    if (!(MARLNAV_AB & 4)) philox2x32_10(r0, r1, native_key(seed, blk, s));  // (AB 4: timing only)
+    philox2x32_10(r0, r1, native_key(seed, blk, s));
 }
 
 // a 32-bit word -> [0, 1) on a 24-bit grid (torch.rand's fp32 values)
@@ -874,7 +842,6 @@ __device__ __forceinline__ void wave_store(float *__restrict__ dst, const float 
 {
     int head = 0;
     const OutBuf ob = out_buf(dst, 4u * n);
-    wt = kWtOut && wt;
     if ((reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
         const int n4 = n >> 2;
         for (int i = lane; i < n4; i += 64) {
@@ -1129,7 +1096,9 @@ __device__ __forceinline__ RowOut observe_row_own(const float *__restrict__ sts,
                                                   float *row, const MarlnavParams &pr, bool &ok)
 {
     const float cap = pr.cap_distance;
-    if constexpr (FAST && MARLNAV_PACKED_PAIRS && !(MARLNAV_AB & 64)) {
+    if constexpr (FAST) {
+        // FAST callers are coordinate-checked: the packed pair math has no
+        // guards and nothing here consumes `ok` for it
         // the row's pairs in row order - target, obstacles, other agents -
         // two per pair2_fast (the same bits as pair_dist/pair_angle<true>,
         // scripts/probes/pair_forms.hip); an odd last pair alone
@@ -1186,16 +1155,17 @@ __device__ __forceinline__ RowOut observe_row_own(const float *__restrict__ sts,
         }
         return out;
     }
-    const float td = pair_dist<FAST>(ox, oy, tge[0], tge[1], ok);
-    const float ta = pair_angle<FAST>(ox, oy, tge[0], tge[1], dx, dy, td, cap, ok);
+    // IEEE pair math, one pair at a time
+    const float td = pair_dist<false>(ox, oy, tge[0], tge[1], ok);
+    const float ta = pair_angle<false>(ox, oy, tge[0], tge[1], dx, dy, td, cap, ok);
     row[0] = ta;
     row[1] = td;
     bool ob_risk = false, ob_col = false;
 #pragma unroll
     for (int j = 0; j < O; ++j) {
         const float px = obe[2 * j], py = obe[2 * j + 1];
-        const float d = pair_dist<FAST>(ox, oy, px, py, ok);
-        row[2 + j] = pair_angle<FAST>(ox, oy, px, py, dx, dy, d, cap, ok);
+        const float d = pair_dist<false>(ox, oy, px, py, ok);
+        row[2 + j] = pair_angle<false>(ox, oy, px, py, dx, dy, d, cap, ok);
         row[2 + O + j] = d;
         if (TERMS) {
             ob_risk |= d < pr.ob_risk_dist;
@@ -1208,8 +1178,8 @@ __device__ __forceinline__ RowOut observe_row_own(const float *__restrict__ sts,
     for (int j = 0; j < A - 1; ++j) {
         const int m = j + (j >= a ? 1 : 0);
         const float px = sts[5 * m], py = sts[5 * m + 1];
-        const float d = pair_dist<FAST>(ox, oy, px, py, ok);
-        row[2 + 2 * O + j] = pair_angle<FAST>(ox, oy, px, py, dx, dy, d, cap, ok);
+        const float d = pair_dist<false>(ox, oy, px, py, ok);
+        row[2 + 2 * O + j] = pair_angle<false>(ox, oy, px, py, dx, dy, d, cap, ok);
         row[2 + 2 * O + (A - 1) + j] = d;
         if (TERMS) {
             ag_risk |= d < pr.ag_risk_dist;
@@ -1220,13 +1190,9 @@ __device__ __forceinline__ RowOut observe_row_own(const float *__restrict__ sts,
     RowOut out{0.0f, 0.0f, 0u};
     if (TERMS) {
         const float *agd = row + 2 + 2 * O + (A - 1);  // the others_distances just written
-        float bond;
-        if (FAST && (pr.flags & kTermsFastFlag))
-            bond = torch_row_sum_r<A - 1>(agd, [&](float d) { return bond_term<true, REFC>(d, pr, ok); });
-        else
-            bond = torch_row_sum_r<A - 1>(agd, [&](float d) { return bond_term<false>(d, pr, ok); });
-        out = row_reward<A, FAST, REFC>(ta, td, ob_risk || ag_risk, ob_col || ag_col, band, bond, pr,
-                                        ok);
+        const float bond = torch_row_sum_r<A - 1>(agd, [&](float d) { return bond_term<false>(d, pr, ok); });
+        out = row_reward<A, false, REFC>(ta, td, ob_risk || ag_risk, ob_col || ag_col, band, bond,
+                                         pr, ok);
     }
     return out;
 }
@@ -1246,7 +1212,7 @@ __device__ __forceinline__ RowOut observe_row_regs(const float *__restrict__ sts
 template <int D>
 __device__ __forceinline__ void store_row(float *__restrict__ dst, const float *row, bool wt)
 {
-    if (kWtOut && wt) {
+    if (wt) {
         // per-lane row pointers: one written-through buffer from the first
         // active lane's row
         const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)dst);

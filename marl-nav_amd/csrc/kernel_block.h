@@ -90,7 +90,7 @@ __device__ __forceinline__ void block_store(float *__restrict__ dst, const float
                                             int n, int tid, int nt, bool wt)
 {
     const int n4 = n >> 2;
-    if (kWtOut && wt) {
+    if (wt) {
         const OutBuf ob = out_buf(dst, (uint32_t)n * 4u);
         for (int i = tid; i < n4; i += nt)
             wt_st4(ob, 16u * i, reinterpret_cast<const float4 *>(src)[i]);
@@ -121,7 +121,7 @@ __device__ __forceinline__ void block_store2(float *__restrict__ d1, const float
     for (int k = 0; k < K2; ++k)
         if ((k + 1) * NT <= Q2 || tid + k * NT < Q2)
             v2[k] = reinterpret_cast<const float4 *>(s2)[tid + k * NT];
-    if (kWtOut && wt) {
+    if (wt) {
         const OutBuf o1 = out_buf(d1, N1 * 4), o2 = out_buf(d2, N2 * 4);
 #pragma unroll
         for (int k = 0; k < K1; ++k)
@@ -186,9 +186,8 @@ __device__ __forceinline__ EnvEnd env_end(F flag, float step_num_old, uint8_t te
 // replay and stream launches): 65536x3x3 -0.03 to -0.04 us, 131072x3x3 -0.10 to
 // -0.15, 32768x3x3 +0.01, but the draw-wave instantiation (16384x3x3, one
 // block per CU) +0.08: so every instantiation but the draw-wave one.
-// MARLNAV_EARLY_OUT 0 / 1 forces it (A/B builds).
 template <int A, int O, bool HELP>
-constexpr bool kBlockEarlyOut = MARLNAV_EARLY_OUT < 0 ? (O >= 8 || !HELP) : MARLNAV_EARLY_OUT != 0;
+constexpr bool kBlockEarlyOut = O >= 8 || !HELP;
 
 // Phases (one block barrier after each of the first four): stage | move +
 // coordinate check | observe into LDS rows | per-env phase on wave 0 while
@@ -216,7 +215,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
     unsigned long long t_entry;
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_entry));
 #endif
-    if (MARLNAV_AB & 4096) return;  // (AB 4096: timing only - the launch alone)
+    if (MARLNAV_AB & 4096) return;  // (AB 4096: the launch alone)
     const int tid = (int)threadIdx.x;
     const unsigned lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // agent of this wave
@@ -300,7 +299,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
     if constexpr (HELP) {
         // the draw wave: the same draws, O per lane (env `lane`), on the
         // SIMD the agent waves leave idle
-        if (hw && overlap && !(MARLNAV_AB & 256) && (int)lane < ne) {
+        if (hw && overlap && (int)lane < ne) {
             KArgsK *kl = kargs_late<kHotKargsOff>();
             const uint64_t sidx = kl->a.step_idx, g = (uint64_t)(kl->a.env_offset + e0) + lane;
             float *pre = lds + BP::FRESH;
@@ -315,7 +314,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
                 pre[(2 * j + 1) * E + lane] = v[j][1];
             }
         }
-    } else if (kPre && overlap && !(MARLNAV_AB & 256)) {  // (AB 256: timing only, no draws)
+    } else if (kPre && overlap) {
         // the fresh obstacles of every env of the block (its Philox draws
         // depend only on seed, step and env id), drawn while the staging
         // loads are in flight: a finished env's re-init then reads them
@@ -376,7 +375,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
     STAMPS_S(2);  // (substamps: every span this wave issued landed)
     __syncthreads();
     STAMP(1);
-    if (MARLNAV_AB & 8192) {  // (AB 8192: timing / census only - staged, then exit;
+    if (MARLNAV_AB & 8192) {  // (AB 8192: staged, then exit;
         asm volatile("" ::"v"(sn), "v"(c), "v"(a1));  // the sin/cos kept alive)
         return;
     }
@@ -446,8 +445,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
         float rowv[D];
         RowOut ro;
         bool unused = true;
-        if (__builtin_expect(fast, 1) && !MARLNAV_AB_NOREFC && pr.bond_sharpness == 1.0f &&
-            pr.max_at_prop_d == 2.0f)
+        if (__builtin_expect(fast, 1) && pr.bond_sharpness == 1.0f && pr.max_at_prop_d == 2.0f)
             ro = observe_row_own<A, O, !OBS_ONLY, true, true>(st + 5 * A * l, lds + BP::OB + 2 * O * l,
                                                               lds + BP::TG + 2 * l, w, ox, oy, dx,
                                                               dy, rowv, pr, unused);
@@ -468,14 +466,12 @@ __global__ void __launch_bounds__(64 * (A + HELP))
     }
     __syncthreads();
     STAMP(3);
-    if (MARLNAV_AB & 16384) return;  // (AB 16384: timing only - observed, then exit)
+    if (MARLNAV_AB & 16384) return;  // (AB 16384: observed, then exit)
     // the output pointers, read again from the kernarg segment here: no
     // scalar register holds them through the observation, where the entry
     // copies spilled 14 SGPRs to VGPR lanes (65536x3x3 6.55 -> 6.33 us,
-    // profiles/r05_ab_late_ptrs.txt; MARLNAV_LATE_PTRS=0: the entry copies)
-    StepPtrs bo;
-    if constexpr (MARLNAV_LATE_PTRS) bo = load_ptrs(kargs_late<kHotKargsOff>());
-    else bo = b;
+    // profiles/r05_ab_late_ptrs.txt)
+    const StepPtrs bo = load_ptrs(kargs_late<kHotKargsOff>());
     float *gobs = in_sgpr(bo.obs + e0 * (A * D));
     if (OBS_ONLY) block_store(gobs, obs_rows, nrow * D, tid, NT, wt);
     const bool norm = !OBS_ONLY && (pr.flags & MARLNAV_WRITE_OBS_NORM);
@@ -490,7 +486,11 @@ __global__ void __launch_bounds__(64 * (A + HELP))
         const BlockEnvs<A, O, D> ev{st, lds + BP::OB, lds + BP::TG, obs_rows, e0};
         // ---- per-env reductions, terminal logic (wave 0, one lane per env)
         if (w == 0) {
-            if (MARLNAV_ENV_PRIO) __builtin_amdgcn_s_setprio(MARLNAV_ENV_PRIO);  // (A/B builds)
+            // the block's latency chain while its other waves wait at the
+            // barrier: above the other blocks' waves on its SIMD (0 -> 3:
+            // 65536x3x3 7.00 -> 6.95 us steady, 7.24 -> 7.16 fresh, 16384x3x3
+            // 5.34 -> 5.30 / 5.36 -> 5.34; profiles/r04_ab_env_prio.txt)
+            __builtin_amdgcn_s_setprio(3);
             const bool env_on = l < ne;
             bool fin = false, tr_l = false, co_l = false, ta_l = false;
             if (env_on) {
@@ -545,12 +545,15 @@ __global__ void __launch_bounds__(64 * (A + HELP))
                 }
                 const float sn_out = fin ? blend_in(step_num, 0.0f) : step_num;
                 const uint8_t tm_out = (uint8_t)(!term_old && all_in);  // :218-219
-                if (MARLNAV_AB & 1024) {  // (AB 1024: timing only, no per-env stores)
-                } else if (MARLNAV_ENV_OUT && wt && full) {
+                if (wt && full) {
                     // written through, 32-bit buffer offsets from the block's
                     // first env: no dirty L2 lines left for the end-of-launch
-                    // write-back, and no 64-bit address math per store
-                    // (MARLNAV_ENV_OUT, marlnav_debug.h)
+                    // write-back, and no 64-bit address math per store (plain
+                    // -> written through, graph replay, steady: 65536x3x3 6.84
+                    // -> 6.70 us, 16384x3x3 5.01 -> 4.99, 32768x3x3 and
+                    // 131072x3x8 unchanged, profiles/r05_ab_envout.txt; staged
+                    // in LDS and stored as 16-byte pieces beside the block
+                    // store: slower, 6.94, 5.13, 17.89 us)
                     wt_st(out_buf(bo.reward + e0, 4 * E), 4u * l, rmean);
                     wt_st(out_buf(bo.terminates + e0, E), (uint32_t)l, tm_out);
                     wt_st(out_buf(bo.terminated + e0, E), (uint32_t)l, (uint8_t)terminated);
@@ -578,7 +581,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
             const unsigned c_tar = __popcll(__ballot(ta_l));
             if (lane == 0) {
                 flg[0] = (int)__popcll(finmask);
-                if ((c_trunc | c_col | c_tar) && !(MARLNAV_AB & 512)) {  // (AB 512: timing only)
+                if (c_trunc | c_col | c_tar) {
                     KArgsK *kl = kargs_late<kHotKargsOff>();
                     uint64_t *cnt = kl->a.b.counters;
                     const int64_t slots = kl->a.waves;
@@ -591,7 +594,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
                 }
             }
             STAMPX(2);  // (wave 0: list, counts and counters done)
-            if (MARLNAV_ENV_PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
         } else if (overlap && !hw) {
             // ---- waves 1..A-1, while wave 0 runs the per-env phase: the
             // finished set from the inputs wave 0 uses (red flags, step_num,
@@ -607,25 +610,28 @@ __global__ void __launch_bounds__(64 * (A + HELP))
             }
             const uint64_t fm = __ballot(fin);
             early = kBlockEarlyOut<A, O, HELP> && full && !norm && fm == 0ull;
-            if (early && !(MARLNAV_AB & 2))
+            if (early && !(MARLNAV_AB & 2))  // (AB 2: everything but the final stores)
                 block_store2<E * A * D, E * A * 5, NT - 64>(
                     gobs, obs_rows, in_sgpr(bo.states_out + e0 * (A * 5)), st, tid - 64, wt);
             STAMPX(0);
-            if (fm && !(MARLNAV_AB & 1)) {
-                if (MARLNAV_REINIT_PRIO) __builtin_amdgcn_s_setprio(MARLNAV_REINIT_PRIO);  // (A/B builds)
+            if (fm) {
                 STAMPX(1);
-                // kTailOut: the pass's obstacle / target outputs through the
+                // kTailOut: where the fresh obstacles are drawn at stage time
+                // (kPre), the pass's obstacle / target outputs go through the
                 // block's SGPR pointers, written through (no dirty L2 lines
-                // for the end-of-launch write-back)
-                constexpr int kTailOut = MARLNAV_TAIL_PTRS >= 0 ? MARLNAV_TAIL_PTRS : (kPre ? 2 : 0);
-                const TailOut tout{bo.obstacles, bo.target, e0, kTailOut == 2 && wt && full};
+                // for the end-of-launch write-back); else through kargs loads
+                // as plain stores. Graph replay, steady, plain -> this:
+                // 16384x3x3 5.01 -> 4.89 us, 32768x3x3 5.70 -> 5.55, 65536x3x3
+                // 6.70 -> 6.70, but 131072x3x8 (16 obstacle stores per
+                // finished env) 17.12 -> 17.89 (profiles/r05_ab_tp2rp.txt)
+                constexpr bool kTailOut = kPre;
+                const TailOut tout{bo.obstacles, bo.target, e0, wt && full};
                 reinit_reobs_native<A, O, kPre ? E : 0>(kargs_late<kHotKargsOff>(), ev,
                                                         lds + BP::FORM, MaskList{fm},
                                                         (int)__popcll(fm), pr.cap_distance,
                                                         tid - 64, NT - 64, lds + BP::FRESH,
                                                         kTailOut ? &tout : nullptr);
                 STAMPX(2);
-                if (MARLNAV_REINIT_PRIO) __builtin_amdgcn_s_setprio(0);
             }
         }
         __syncthreads();
@@ -674,7 +680,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
         for (int k = 0; k < K; ++k) v[k] = (v[k] - m) / sc;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            if (kWtOut && wt)
+            if (wt)
                 wt_st(out_buf(gn, E * A * D * 4), 4u * (tid + k * NT), v[k]);
             else
                 out_st<kNtRows>(gn + tid + k * NT, v[k]);
@@ -698,7 +704,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
             for (int i = tid; i < nrow * D; i += NT) {
                 const int kk = i % D;
                 const float v = (obs_rows[i] - ms[kk]) / ms[D + kk];
-                if (kWtOut && wt)
+                if (wt)
                     wt_st(nb, 4u * i, v);
                 else
                     gn[i] = v;

@@ -275,11 +275,9 @@ __device__ __forceinline__ void native_pair_item(KArgsK *kl, const Envs &ev, con
     using IT = NativeItems<A, O>;
     const int ag = kk / IT::NP, p = kk - ag * IT::NP;
     uint32_t ux = 0u, uy = 0u;
-    const bool cargs = (MARLNAV_AB & 8) != 0;  // timing only: no kernel-argument loads
     if (!E && p >= 1 && p <= O)  // obstacle p - 1: its Philox block
-        native_block(cargs ? 5u : kl->p.seed, (uint32_t)(p - 1),
-                     (uint64_t)((cargs ? 0 : kl->a.env_offset) + ev.env(c)),
-                     cargs ? 7u : kl->a.step_idx, ux, uy);
+        native_block(kl->p.seed, (uint32_t)(p - 1), (uint64_t)(kl->a.env_offset + ev.env(c)),
+                     kl->a.step_idx, ux, uy);
     // inputs: the blend of the env's current value (LDS; other items may be
     // blending it in place meanwhile - blend_in is idempotent) with its fresh
     // value (template or Philox draw)
@@ -300,8 +298,8 @@ __device__ __forceinline__ void native_pair_item(KArgsK *kl, const Envs &ev, con
             px = blend_in(oo[0], pre[(2 * (p - 1)) * E + c]);
             py = blend_in(oo[1], pre[(2 * (p - 1) + 1) * E + c]);
         } else {
-            const float rx = cargs ? 1000.f : kl->p.obs_range_x, mx = cargs ? 0.f : kl->p.obs_mean_x;
-            const float ry = cargs ? 1000.f : kl->p.obs_range_y, my = cargs ? 0.f : kl->p.obs_mean_y;
+            const float rx = kl->p.obs_range_x, mx = kl->p.obs_mean_x;
+            const float ry = kl->p.obs_range_y, my = kl->p.obs_mean_y;
             px = blend_in(oo[0], rx * (native_u24(ux) - 0.5f) + mx);
             py = blend_in(oo[1], ry * (native_u24(uy) - 0.5f) + my);
         }
@@ -320,10 +318,7 @@ __device__ __forceinline__ void native_pair_item(KArgsK *kl, const Envs &ev, con
     const bool cok = coord_ok(ox) && coord_ok(oy) && coord_ok(px) && coord_ok(py);
     bool unused = true;
     float d, ang;
-    if (MARLNAV_AB & 16) {  // timing only: no pair math
-        d = px + ox + dx;
-        ang = py + oy + dy;
-    } else if (__ballot(on && !cok) == 0ull) {
+    if (__ballot(on && !cok) == 0ull) {
         d = pair_dist<true>(ox, oy, px, py, unused);
         ang = pair_angle<true>(ox, oy, px, py, dx, dy, d, cap, unused);
     } else {
@@ -354,7 +349,7 @@ __device__ __forceinline__ void tail_out(const TailOut *to, KArgsK *kl, bool obs
 {
     if (to == nullptr) {
         out_el(obst ? kl->a.b.obstacles : kl->a.b.target, idx, v);
-    } else if (kWtOut && to->wt) {
+    } else if (to->wt) {
         const int64_t base = obst ? to->e0 * O * 2 : to->e0 * 2;
         const uint32_t span = obst ? 64u * O * 2 * 4 : 64u * 2 * 4;
         wt_st(out_buf((obst ? to->gob : to->gtg) + base, span), (uint32_t)(idx - base) * 4u, v);
@@ -429,10 +424,10 @@ __device__ __forceinline__ void reinit_reobs_tpl(KArgsK *kl, const Envs &ev, con
     const float rx = kl->p.obs_range_x, mx = kl->p.obs_mean_x;
     const float ry = kl->p.obs_range_y, my = kl->p.obs_mean_y;
     const int j = tid % O, ag0 = tid / O;
-    if constexpr (MARLNAV_TPL_LOADS_FIRST && A * A <= NT && 5 * A + 2 <= NT) {
-        // (A/B) every LDS read of the pass first, then the Philox block and
-        // the pair math, then every write: one LDS round trip in front of
-        // the chain instead of one per step
+    if constexpr (A * A <= NT && 5 * A + 2 <= NT) {
+        // every LDS read of the pass first, then the Philox block and the
+        // pair math, then every write: one LDS round trip in front of the
+        // chain instead of one per step
         constexpr int KA = (A + agd - 1) / agd;
         for (int fe = 0; fe < nfin; ++fe) {
             const int c = list[fe];
@@ -621,7 +616,6 @@ __device__ __forceinline__ void reinit_reobs_native(KArgsK *kl, const Envs &ev, 
     if (nwv >= 2) {
         const int pw = nwv >> 1;  // waves [0, pw): pair items; [pw, nwv): the rest
         if (wv < pw) {
-            if (MARLNAV_AB & (1 << 18)) return;  // (timing only: no pair items)
             const int n = nfin * IT::NPAIR;
             for (int base = 64 * wv; base < n; base += 64 * pw) {
                 const int i = base + lane;
@@ -633,7 +627,6 @@ __device__ __forceinline__ void reinit_reobs_native(KArgsK *kl, const Envs &ev, 
                                           ic - fe * IT::NPAIR, on, cap);
             }
         } else {
-            if (MARLNAV_AB & (1 << 17)) return;  // (timing only: no template / obstacle items)
             const int n = nfin * IT::NREST;
             for (int base = 64 * (wv - pw); base < n; base += 64 * (nwv - pw)) {
                 const int i = base + lane;

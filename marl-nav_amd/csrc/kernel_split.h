@@ -96,10 +96,9 @@ constexpr bool kSplitTpl = kSplitSpread<A, O> && O > 8;
 // the end of the pair phase (few-obstacle shapes: 1024x3x8 5.09 -> 5.00 us,
 // A/B in profiles/r03_ab_logs2.txt), or, for the workgroup-spread
 // many-obstacle shapes, on wave 0 after the per-env barrier, one lane per row
-// (4096x16x32 11.76 vs 11.84 us on the row leaders). MARLNAV_SPLIT_RR_LEADER
-// (A/B builds) forces the row leaders everywhere.
+// (4096x16x32 11.76 vs 11.84 us on the row leaders).
 template <int A, int O>
-constexpr bool kSplitRRLeader = !kSplitSpread<A, O> || O <= 8 || MARLNAV_SPLIT_RR_LEADER;
+constexpr bool kSplitRRLeader = !kSplitSpread<A, O> || O <= 8;
 
 // ... re-initialised and re-observed in one pass (reinit_reobs_tpl: the
 // workgroup's threads cover whole obstacle columns)
@@ -185,9 +184,7 @@ struct SplitPlan {
     // obstacle draws of the workgroup's EW envs, component k of obstacle j of
     // env code c at PRE + (2j + k) * EW + c (native_obst_draw, device_math.h)
     static constexpr int EW = kWavesPerBlock * EPW;
-    // (kSplitSpread shapes with O <= 8: the formation alone at FTP, for the
-    // fused native re-init pass: MARLNAV_SPLIT_FORM_LDS)
-    static constexpr int PRE = (FTP + (kSplitTpl<A, O> ? NCP : (kSplitSpread<A, O> && O <= 8 && MARLNAV_SPLIT_FORM_LDS ? NF : 0)) + 3) & ~3;
+    static constexpr int PRE = (FTP + (kSplitTpl<A, O> ? NCP : 0) + 3) & ~3;
     static constexpr int BLK = PRE + (kSplitSpread<A, O> && O <= 8 ? 2 * O * EW : 0);
     static_assert(EPW >= 1, "an env's rows must fit one wave");
 };
@@ -247,10 +244,6 @@ struct SplitTerms {
     float ta, td;
 };
 
-// Occupancy the register allocator may assume (waves per SIMD): the grids
-// below run at most 3-4 waves per SIMD, so the default target of 8 only
-// costs instruction-level parallelism (timing builds set these).
-
 // The target pair takes a spare slot of lane LPR-1 when the other agents (or
 // else the obstacles) do not divide over the LPR lanes: one pair body fewer per
 // wave (A16/O32: 13 -> 12, A3/O8: 4 -> 3); the row leader reads the target
@@ -259,8 +252,6 @@ template <int A, int O, int LPR>
 constexpr bool kSplitTgtInAg = (A - 1) % LPR != 0;
 template <int A, int O, int LPR>
 constexpr bool kSplitTgtInOb = !kSplitTgtInAg<A, O, LPR> && O % LPR != 0;
-
-// unroll factor of split_pairs' obstacle / other-agent loops (timing builds)
 
 template <int A, int O, int LPR, bool TERMS, bool FAST, bool TFAST = false, bool SHARP1 = false>
 __device__ __forceinline__ SplitTerms split_pairs(const float *__restrict__ sts,
@@ -286,91 +277,9 @@ __device__ __forceinline__ SplitTerms split_pairs(const float *__restrict__ sts,
     // SHARP1: bond_sharpness == 1 (the reference's constant, environment.py:
     // 66), where (d - ideal) / 1 is d - ideal exactly
     if constexpr (TERMS && TFAST && !SHARP1) d_sharp = make_divc(pr.bond_sharpness, ok);
-    if constexpr (FAST && MARLNAV_PACKED_SPLIT && !(MARLNAV_AB & 64)) {
-        // every slot's pair first - two per pair2_fast (pairs_fast); a slot
-        // with no pair (j >= O, or kx >= A - 1 off the target lane) computes
-        // a discarded one - then the row writes and terms of the loops below
-        constexpr bool TS = !kSplitTgtInAg<A, O, LPR> && !kSplitTgtInOb<A, O, LPR>;
-        constexpr int T0 = TS ? 1 : 0, N = T0 + SP::NOB + SP::NAG;
-        float px[N], py[N], pd[N], pg[N];
-        if constexpr (TS) {
-            px[0] = tge[0];
-            py[0] = tge[1];
-        }
-#pragma unroll
-        for (int i = 0; i < SP::NOB; ++i) {
-            const int j = q + LPR * i;
-            const bool valid = O % LPR == 0 || j < O;
-            const bool tgt = kSplitTgtInOb<A, O, LPR> && i == SP::NOB - 1 && q == TQ;
-            const float *pt = tgt ? tge : obe + 2 * (valid ? j : 0);
-            px[T0 + i] = pt[0];
-            py[T0 + i] = pt[1];
-        }
-#pragma unroll
-        for (int i = 0; i < SP::NAG; ++i) {
-            const int kx = q + LPR * i;
-            const bool valid = (A - 1) % LPR == 0 || kx < A - 1;
-            const bool tgt = kSplitTgtInAg<A, O, LPR> && i == SP::NAG - 1 && q == TQ;
-            const int m = valid ? kx + (kx >= a ? 1 : 0) : 0;
-            const float *pt = tgt ? tge : sts + 5 * m;
-            px[T0 + SP::NOB + i] = pt[0];
-            py[T0 + SP::NOB + i] = pt[1];
-        }
-        pairs_fast<N>(ox, oy, dx, dy, px, py, cap, pd, pg);
-        if constexpr (TS) {
-            t.ta = pg[0];
-            t.td = pd[0];
-            if (q == 0) {
-                orow[0] = pg[0];
-                orow[1] = pd[0];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < SP::NOB; ++i) {
-            const int j = q + LPR * i;
-            const bool valid = O % LPR == 0 || j < O;
-            const bool tgt = kSplitTgtInOb<A, O, LPR> && i == SP::NOB - 1 && q == TQ;
-            const float d = pd[T0 + i], ang = pg[T0 + i];
-            if (valid) {
-                orow[2 + j] = ang;
-                orow[2 + O + j] = d;
-                if (TERMS) ob_min = __builtin_fminf(ob_min, d);
-            } else if (tgt) {
-                orow[0] = ang;
-                orow[1] = d;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < SP::NAG; ++i) {
-            const int kx = q + LPR * i;
-            const bool valid = (A - 1) % LPR == 0 || kx < A - 1;
-            const bool tgt = kSplitTgtInAg<A, O, LPR> && i == SP::NAG - 1 && q == TQ;
-            const float d = pd[T0 + SP::NOB + i], ang = pg[T0 + SP::NOB + i];
-            if (valid) {
-                orow[2 + 2 * O + kx] = ang;
-                orow[2 + 2 * O + (A - 1) + kx] = d;
-                if (TERMS) {
-                    ag_min = __builtin_fminf(ag_min, d);
-                    t.band += (pr.agents_min_d < d && d < pr.agents_max_d) ? 1 : 0;
-                    if constexpr (TFAST) {
-                        const float sd = SHARP1 ? d - pr.ideal_dist
-                                                : div_c(d - pr.ideal_dist, d_sharp, ok);
-                        bond_row[kx] = recip_fast(1.0f + sd * sd, ok);
-                    } else {
-                        const float sd = (d - pr.ideal_dist) / pr.bond_sharpness;
-                        bond_row[kx] = 1.0f / (1.0f + sd * sd);
-                    }
-                }
-            } else if (tgt) {
-                orow[0] = ang;
-                orow[1] = d;
-            }
-        }
-        if (TERMS)
-            t.fl |= (ob_min < pr.ob_risk_dist ? 1u : 0u) | (ob_min < pr.ob_coll_dist ? 2u : 0u) |
-                    (ag_min < pr.ag_risk_dist ? 4u : 0u) | (ag_min < pr.ag_coll_dist ? 8u : 0u);
-        return t;
-    }
+    // (one pair per VALU instruction: the packed pair math of the env-block
+    // kernel, pairs_fast, measured slower here - 4096x16x32 11.19 -> 11.33 us,
+    // 1024x3x8 and 2048x16x32 unchanged, profiles/r06_ab_packed_split.txt)
     if constexpr (!kSplitTgtInAg<A, O, LPR> && !kSplitTgtInOb<A, O, LPR>) {
         const float d = pair_dist<FAST>(ox, oy, tge[0], tge[1], ok);
         const float ang = pair_angle<FAST>(ox, oy, tge[0], tge[1], dx, dy, d, cap, ok);
@@ -466,7 +375,7 @@ struct OneEnv {
 template <int A, int O, int LPR>
 constexpr bool kSplitOwnShape = kSplitTplPass<A, O> && 64 / LPR / A == 1;
 template <int A, int O, int LPR, bool OWN>
-constexpr bool kSplitOwn = kSplitOwnShape<A, O, LPR> && (OWN || MARLNAV_SPLIT_OWN);
+constexpr bool kSplitOwn = kSplitOwnShape<A, O, LPR> && OWN;
 
 template <int A, int O, int LPR>
 struct SplitSlots {
@@ -655,7 +564,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
     // the own-wave path stores raw row terms for wave 0's row_reward, which
     // wave 0 applies only when the row leaders do not (kSplitRRLeader)
     static_assert(!kSplitOwn<A, O, LPR, OWN> || !kSplitRRLeader<A, O>,
-                  "kSplitOwn needs wave 0's row rewards (MARLNAV_SPLIT_RR_LEADER=0)");
+                  "kSplitOwn needs wave 0's row rewards");
     (void)k;  // read through kargs_late<kHotKargsOff>()
     extern __shared__ __attribute__((aligned(16))) float lds[];
 #if MARLNAV_STAMPS
@@ -682,7 +591,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
     b.step_num = const_cast<float *>(h_step_num);
     b.terminates = const_cast<uint8_t *>(h_terminates);
     STAMP(0);
-    if (MARLNAV_AB & 4096) return;  // (AB 4096: timing only - the launch alone)
+    if (MARLNAV_AB & 4096) return;  // (AB 4096: the launch alone)
     float *wl = lds + wib * SP::FLOATS;
     float *st = wl + SP::ST;
     const int64_t e0 = tile * EPW;
@@ -703,21 +612,6 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
         copy_span(b.obstacles + e0 * (O * 2), wl + SP::OB, ne * O * 2, (int)lane);
         copy_span(b.target + e0 * 2, wl + SP::TG, ne * 2, (int)lane);
     }
-    // kPre shapes (native re-init): the formation into FTP by LDS-DMA from
-    // wave 0 (always live), with the tile's spans (the stage wait covers it),
-    // for the fused re-init pass, whose pair items otherwise read it from
-    // global memory after the per-env barrier
-    constexpr bool kFormLds = kSplitSpread<A, O> && O <= 8 && MARLNAV_SPLIT_FORM_LDS && SP::NF <= 64;
-    bool form_lds = false;
-    if constexpr (kFormLds && !NOISY && !OBS_ONLY) {
-        KArgsK *kl = kargs_late<kHotKargsOff>();
-        const float *cfo = kl->a.b.formation;
-        form_lds = cfo && !kl->a.b.fresh_states;
-        if (form_lds && wib == 0 && lane < (unsigned)SP::NF)
-            __builtin_amdgcn_global_load_lds(cfo + lane,
-                                             (LdsVoid *)(lds + kWavesPerBlock * SP::FLOATS + SP::FTP),
-                                             4, 0, 0);
-    }
     const bool env_on = (int)lane < ne;
     float sn_in = 0.0f;
     unsigned term_in = 0u;
@@ -726,12 +620,12 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
         term_in = b.terminates[e0 + lane];
     }
     MarlnavParams pr = load_params(K);
-    if constexpr (MARLNAV_OWN_VPIN == 2 || (MARLNAV_OWN_VPIN && kSplitOwn<A, O, LPR, OWN>)) {
+    if constexpr (kSplitOwn<A, O, LPR, OWN>) {
         // the pair loops' and reward terms' parameters held in VGPRs: the
         // own-wave instantiation otherwise runs out of SGPRs (59 spilled to
         // VGPR lanes, reloaded in the observation's hot blocks; 20 left, in
-        // cold blocks). Every split kernel (MARLNAV_OWN_VPIN 2): 4096x16x32
-        // 11.23 -> 11.30 us, not taken
+        // cold blocks). The same in every split kernel: 4096x16x32 11.23 ->
+        // 11.30 us, not taken
         const auto pin = [](float &x) { asm volatile("" : "+v"(x)); };
         pin(pr.ob_risk_dist); pin(pr.ob_coll_dist); pin(pr.ag_risk_dist); pin(pr.ag_coll_dist);
         pin(pr.agents_min_d); pin(pr.agents_max_d); pin(pr.ideal_dist); pin(pr.bond_sharpness);
@@ -779,7 +673,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // LDS-DMA landed
     wave_sync();
     STAMP(1);
-    if (MARLNAV_AB & 8192) return;  // (AB 8192: timing only - staged, then exit)
+    if (MARLNAV_AB & 8192) return;  // (AB 8192: staged, then exit)
 
     // kSplitTpl (native re-init): the formation and its observation template
     // (NCP floats) into registers now, a few per thread, so their loads run
@@ -915,8 +809,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
             const float sn0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sn_in), 0));
             const unsigned tm0 = (unsigned)__builtin_amdgcn_readlane((int)term_in, 0);
             const bool col = __ballot(row_on && (fl & 10u) != 0u) != 0ull;
-            const bool own_fin = tpl_on && !(MARLNAV_AB & 1) &&
-                                 (sn0 + 1.0f > pr.trunc_after || tm0 != 0u || col);
+            const bool own_fin = tpl_on && (sn0 + 1.0f > pr.trunc_after || tm0 != 0u || col);
             if (!own_fin) {
                 if (__builtin_expect(fast, 1))
                     split_bearings<A, O, LPR, true, false>(sts, obe, tge, a, q, ox, oy, dx, dy, orow,
@@ -1057,11 +950,9 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
                 if (VAL % 16 == 0) {
                     for (int i = (int)lane; i < n / 4; i += 64) {
                         const int rr = i / D4, c4 = i - rr * D4;
-                        // (AB 2048: timing only - consecutive pieces, no bank
-                        // conflicts: the most an XOR swizzle of the pieces can save)
-                        const float4 v = *reinterpret_cast<const float4 *>(
-                            (MARLNAV_AB & 2048) ? src + 4 * i : src + rr * SP::DP + 4 * c4);
-                        if (kWtOut && wt)
+                        const float4 v =
+                            *reinterpret_cast<const float4 *>(src + rr * SP::DP + 4 * c4);
+                        if (wt)
                             wt_st4(out_buf(gobs, 4u * n), 16u * i, v);
                         else
                             out_st4<kNtRows>(gobs + 4 * i, v);
@@ -1070,7 +961,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
                     for (int i = (int)lane; i < n; i += 64) {
                         const int rr = i / D;
                         const float v = src[rr * SP::DP + (i - rr * D)];
-                        if (kWtOut && wt)
+                        if (wt)
                             wt_st(out_buf(gobs, 4u * n), 4u * i, v);
                         else
                             out_st<kNtRows>(gobs + i, v);
@@ -1079,7 +970,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
             } else if (VAL % 16 == 0 && ne == EPW) {
                 for (int i = (int)lane; i < n / 4; i += 64) {
                     const float4 v = reinterpret_cast<const float4 *>(src)[i];
-                    if (kWtOut && wt)
+                    if (wt)
                         wt_st4(out_buf(gobs, 4u * n), 16u * i, v);
                     else
                         out_st4<kNtRows>(gobs + 4 * i, v);
@@ -1087,14 +978,14 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
             } else if (VAL % 8 == 0 && n % 2 == 0) {
                 for (int i = (int)lane; i < n / 2; i += 64) {
                     const float2 v = reinterpret_cast<const float2 *>(src)[i];
-                    if (kWtOut && wt)
+                    if (wt)
                         wt_st2(out_buf(gobs, 4u * n), 8u * i, v);
                     else
                         out_st2<kNtRows>(gobs + 2 * i, v);
                 }
             } else {
                 for (int i = (int)lane; i < n; i += 64) {
-                    if (kWtOut && wt)
+                    if (wt)
                         wt_st(out_buf(gobs, 4u * n), 4u * i, src[i]);
                     else
                         out_st<kNtRows>(gobs + i, src[i]);
@@ -1106,7 +997,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
                 for (int i = (int)lane; i < n; i += 64) {
                     const int rr = i / D, kk = i - rr * D;
                     const float v = (src[rr * SP::DP + kk] - mean[kk]) / scale[kk];
-                    if (kWtOut && wt)
+                    if (wt)
                         wt_st(nb, 4u * i, v);
                     else
                         gnorm[i] = v;
@@ -1120,14 +1011,14 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
             if (SAL % 16 == 0 && ne == EPW) {
                 for (int i = (int)lane; i < n / 4; i += 64) {
                     const float4 v = reinterpret_cast<const float4 *>(st)[i];
-                    if (kWtOut && wt)
+                    if (wt)
                         wt_st4(out_buf(gst, 4u * n), 16u * i, v);
                     else
                         out_st4<kNtRows>(gst + 4 * i, v);
                 }
             } else {
                 for (int i = (int)lane; i < n; i += 64) {
-                    if (kWtOut && wt)
+                    if (wt)
                         wt_st(out_buf(gst, 4u * n), 4u * i, st[i]);
                     else
                         out_st<kNtRows>(gst + i, st[i]);
@@ -1137,7 +1028,6 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
     };
 
     bool stored = false;  // (the tile went out before the per-env barrier)
-    bool tail_wg = false;  // (AB 1 << 19, timing only: a workgroup with finished envs skips its stores)
     if (!OBS_ONLY) {
         wave_sync();
         // ---- per-env reductions, terminal logic, masked re-init (env e,
@@ -1238,10 +1128,11 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
                 bsn[wib * EPW + (int)lane] = sn_in;
                 bterm[wib * EPW + (int)lane] = term_in;
             }
-            if constexpr (MARLNAV_SPLIT_EARLY && kSplitOwn<A, O, LPR, OWN>) {
+            if constexpr (kSplitOwn<A, O, LPR, OWN>) {
                 // own-wave re-init: the tile (rows and states) is final here,
-                // so it streams out under wave 0's per-env phase
-                if (tpl_on && !(MARLNAV_AB & 2)) {
+                // so it streams out under wave 0's per-env phase (after it:
+                // 2048x16x32 8.38 -> 8.48 us, profiles/r05_ab_early.txt)
+                if (tpl_on && !(MARLNAV_AB & 2)) {  // (AB 2: everything but the final stores)
                     wave_sync();
                     store_tile();
                     stored = true;
@@ -1249,9 +1140,8 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
             }
             __syncthreads();
             STAMP(4);
-            if (MARLNAV_AB & 16384) return;  // (AB 16384: timing only - observed, then exit)
+            if (MARLNAV_AB & 16384) return;  // (AB 16384: observed, then exit)
             if (wib == 0) {
-                if (MARLNAV_SPLIT_PRIO) __builtin_amdgcn_s_setprio(MARLNAV_SPLIT_PRIO);  // (A/B builds)
                 // every row of the workgroup: its reward terms (one lane per
                 // row, all 64 lanes busy where the row leaders were 1 in LPR)
                 static_assert(kWavesPerBlock * R <= 64, "one lane per row of the workgroup");
@@ -1286,11 +1176,10 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
                 c_col = __popcll(__ballot(co_l));
                 c_tar = __popcll(__ballot(ta_l));
                 STAMPX(1);
-                if (MARLNAV_SPLIT_PRIO) __builtin_amdgcn_s_setprio(0);
             }
             __syncthreads();
             STAMPX(2);
-            if (MARLNAV_AB & 32768) return;  // (AB 32768: timing only - per-env done, then exit)
+            if (MARLNAV_AB & 32768) return;  // (AB 32768: per-env done, then exit)
             const FlatFinList list{bslot, bcnt[0]};
 #if MARLNAV_STAMPS
             stamp_nfin = list.total();
@@ -1300,8 +1189,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
             // (kSplitOwn with the template: every finished env was re-initialised
             // and re-observed by its own wave before the per-env barrier)
             const bool own_done = kSplitOwn<A, O, LPR, OWN> && tpl_on;
-            if ((MARLNAV_AB & (1 << 19)) && list.total()) tail_wg = true;
-            if (const int nfin = ((MARLNAV_AB & 1) || own_done) ? 0 : list.total()) {  // (AB 1: timing only)
+            if (const int nfin = own_done ? 0 : list.total()) {
                 KArgsK *kl = kargs_late<kHotKargsOff>();
                 const SplitEnvs<A, O, EPW, SP::FLOATS, SP::ST, SP::OB, SP::TG, SP::OBS, SP::DP> ev{
                     lds, blk0 * EPW};
@@ -1310,9 +1198,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
                 // fused native re-init + re-observation recomputes a Philox
                 // block per obstacle pair: only for few obstacles
                 if (!NOISY && O <= 8 && !kl->a.b.fresh_states) {
-                    const float *form = form_lds ? lds + kWavesPerBlock * SP::FLOATS + SP::FTP
-                                                 : kl->a.b.formation;
-                    reinit_reobs_native<A, O, SP::EW>(kl, ev, form, list, nfin,
+                    reinit_reobs_native<A, O, SP::EW>(kl, ev, kl->a.b.formation, list, nfin,
                                                       pr.cap_distance, tid, nt, pre);
                     __syncthreads();
                 } else if (kSplitTplPass<A, O> && tpl_on && live == kWavesPerBlock) {
@@ -1378,8 +1264,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock, 4)
 
     // ---- stream the tile out (obs rows and states from LDS)
     wave_sync();
-    if (MARLNAV_AB & 2) return;  // (AB 2: timing only - no store)
-    if ((MARLNAV_AB & (1 << 19)) && tail_wg) return;
+    if (MARLNAV_AB & 2) return;  // (AB 2: everything but the final stores)
     if (!stored) store_tile();
     STAMP(6);
     if (!OBS_ONLY && lane == 0 && (c_trunc | c_col | c_tar)) {

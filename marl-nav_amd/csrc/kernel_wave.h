@@ -103,12 +103,9 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) wave_kernel(StepArgs args
         if (row_on) {
             RowOut ro;
             if constexpr (REGROW) {
-                bool ok = true;
-                ro = observe_row_regs<A_T, O_T, !OBS_ONLY, kGuardedFast>(
+                bool ok = true;  // IEEE pair math (FAST = false) never clears it
+                ro = observe_row_regs<A_T, O_T, !OBS_ONLY, false>(
                     st + 5 * A * el, ob + 2 * S * el, tg + 2 * el, a, rowv, pr, ok);
-                if (__builtin_expect(__ballot(!ok) != 0ull, 0) && !ok)  // IEEE redo, rare
-                    ro = observe_row_regs<A_T, O_T, !OBS_ONLY, false>(
-                        st + 5 * A * el, ob + 2 * S * el, tg + 2 * el, a, rowv, pr, ok);
             } else
                 ro = observe_row<A_T, O_T, !OBS_ONLY>(A, O, st + 5 * A * el, ob + 2 * S * el,
                                                       tg + 2 * el, a, out_row, pr);
@@ -184,11 +181,8 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock) wave_kernel(StepArgs args
                 if (row_on && envbits[el]) {
                     if constexpr (REGROW) {
                         bool ok = true;
-                        observe_row_regs<A_T, O_T, false, kGuardedFast>(st + 5 * A * el, ob + 2 * S * el,
-                                                                tg + 2 * el, a, rowv, pr, ok);
-                        if (!ok)
-                            observe_row_regs<A_T, O_T, false, false>(
-                                st + 5 * A * el, ob + 2 * S * el, tg + 2 * el, a, rowv, pr, ok);
+                        observe_row_regs<A_T, O_T, false, false>(st + 5 * A * el, ob + 2 * S * el,
+                                                                 tg + 2 * el, a, rowv, pr, ok);
                     } else
                         observe_row<A_T, O_T, false>(A, O, st + 5 * A * el, ob + 2 * S * el,
                                                      tg + 2 * el, a, out_row, pr);

@@ -288,10 +288,7 @@ const SplitVariant kSplitVariants[] = {
     MARLNAV_SPLIT_VARIANT(3, 8, 8, false),
     MARLNAV_SPLIT_VARIANT(3, 3, 8, false),
 };
-#ifndef MARLNAV_SPLIT_TINY_WAVES
-#define MARLNAV_SPLIT_TINY_WAVES 256  // (A/B builds)
-#endif
-constexpr int64_t kSplitTinyWaves = MARLNAV_SPLIT_TINY_WAVES;
+constexpr int64_t kSplitTinyWaves = 256;
 // kSplitOwn (a finished env re-initialised by its own wave) for grids of at
 // most two waves per SIMD (one env per wave): same box, graph replay,
 // steady (profiles/r05_ab_tail_own2.txt, r05_ab_tail_ablate.txt): 512x16x32
@@ -299,9 +296,9 @@ constexpr int64_t kSplitTinyWaves = MARLNAV_SPLIT_TINY_WAVES;
 // 4096x16x32 (four waves per SIMD) 11.59-11.62 -> 11.65-11.67. With the
 // one-correction division its register allocation spilled SGPRs into the
 // observation's hot blocks (2048: 9.96 us); with its parameters held in
-// VGPRs (MARLNAV_OWN_VPIN, kernel_split.h) 8.24 us, 1024 7.44, 512 7.28
-// against 9.14 / 7.93 / 7.78 for the default kernel (profiles/r05_ab_vpin.txt)
-constexpr int64_t kSplitOwnMaxEnvs = MARLNAV_SPLIT_OWN_MAX;
+// VGPRs (kernel_split.h) 8.24 us, 1024 7.44, 512 7.28 against 9.14 / 7.93 /
+// 7.78 for the default kernel (profiles/r05_ab_vpin.txt)
+constexpr int64_t kSplitOwnMaxEnvs = 2048;
 #undef MARLNAV_SPLIT_VARIANT
 
 // one-lane-per-row grids below kSplitBelowWaves * (pairs per row / 6) waves
@@ -399,7 +396,7 @@ int device_cus()
 template <int A, int O>
 constexpr BlockFn block_draw_fn()
 {
-    if constexpr (O <= 3 && MARLNAV_DRAW_WAVE) return block_kernel<A, O, false, false, true>;
+    if constexpr (O <= 3) return block_kernel<A, O, false, false, true>;
     else return nullptr;
 }
 
@@ -627,8 +624,7 @@ int marlnav_step(const MarlnavDims *d, const MarlnavParams *pr_in, const Marlnav
     if (family_allowed(MARLNAV_FAMILY_SPLIT))
         if (const SplitVariant *v = select_split(d, args.b, false, fsplit)) {
             g_last_family = MARLNAV_FAMILY_SPLIT;
-            const bool own = !noisy && v->step_own && d->num_parallel <= kSplitOwnMaxEnvs &&
-                             !MARLNAV_SPLIT_OWN_OFF;
+            const bool own = !noisy && v->step_own && d->num_parallel <= kSplitOwnMaxEnvs;
             return launch_split(*v, noisy ? v->noisy : (own ? v->step_own : v->step), args, *pr,
                                 stream, "marlnav_step");
         }

@@ -1,8 +1,9 @@
 #!/bin/bash
-# Build an A/B variant of libmarlnav.so into marl-nav_amd/lib/<name>.so, from
-# the working tree with extra -D flags, or from a git revision:
+# Build a variant of libmarlnav.so into marl-nav_amd/lib/<name>.so, from the
+# working tree with extra -D flags (the diagnostic macros of marlnav_debug.h),
+# or from a git revision (HISTORY.md: where each removed A/B variant's code is):
 #   scripts/build_variant.sh ref HEAD        # the committed kernels
-#   scripts/build_variant.sh exp "" -DSOME_TIMING_SWITCH=1
+#   scripts/build_variant.sh observed "" -DMARLNAV_AB=16384
 # then: LIBS=marl-nav_amd/lib/ref.so bash scripts/cmd_ab.sh (on the GPU box)
 set -eu
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
