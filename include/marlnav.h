@@ -1,6 +1,7 @@
 /*
  * marlnav.h - C ABI of the MI355X (gfx950) environment-step library
- * (libmarlnav.so, built from marl-nav_amd/csrc/marlnav_step.hip).
+ * (libmarlnav.so, built from marl-nav_amd/csrc/marlnav_step.hip,
+ * marlnav_rollout.hip and marlnav_policy.hip).
  *
  * The reference (JussiM01/MARL-nav) has no FFI: its boundary is the Python
  * class `Env` (marlnav/environment.py:8-286). Each entry point below replaces
@@ -34,7 +35,7 @@
 extern "C" {
 #endif
 
-#define MARLNAV_ABI_VERSION 4
+#define MARLNAV_ABI_VERSION 5
 
 /* error codes */
 #define MARLNAV_OK 0
@@ -194,6 +195,58 @@ int64_t marlnav_returns_work_size(int64_t num_parallel);
 int marlnav_discounted_returns(const float *rewards, const uint8_t *done, int64_t T,
                                int64_t P, double gamma, double *returns, double *stats,
                                double *work, void *stream);
+
+/* Shapes of one policy call. D is the env's observation row length,
+ * D = 2 + 2*O + 2*(A-1) for an observed obstacle count O in [1, 256]; H is
+ * the hidden size of both networks (models.py:69-70, `hidden_size`). */
+typedef struct MarlnavPolicyDims {
+    int64_t num_parallel;    /* P  envs in this call                          */
+    int32_t num_agents;      /* A  2 <= A <= 64                               */
+    int32_t obs_dim;         /* D  features per agent row                     */
+    int32_t hidden_size;     /* H  1 <= H <= 512                              */
+    int32_t reserved;        /* must be 0                                     */
+    int64_t env_offset;      /* global id of env 0 of this shard (native RNG) */
+} MarlnavPolicyDims;
+
+/* Device pointers of one policy call, fp32, contiguous. The ten weight and
+ * bias pointers are the LIVE parameter tensors in nn.Linear's own layout
+ * (weight (out, in) row-major): nothing is cached between calls. */
+typedef struct MarlnavPolicyBuffers {
+    const float *obs_norm;     /* (P, A, D) normalised observations           */
+    /* Actor (models.py:20-25) */
+    const float *actor_fc1_w;  /* (H, D)                                      */
+    const float *actor_fc1_b;  /* (H,)                                        */
+    const float *actor_mu_w;   /* (2, H)                                      */
+    const float *actor_mu_b;   /* (2,)                                        */
+    const float *actor_std_w;  /* (2, H)                                      */
+    const float *actor_std_b;  /* (2,)                                        */
+    /* Critic (models.py:45-49) */
+    const float *critic_fc1_w; /* (H, A*D)                                    */
+    const float *critic_fc1_b; /* (H,)                                        */
+    const float *critic_fc2_w; /* (1, H)                                      */
+    const float *critic_fc2_b; /* (1,)                                        */
+    /* standard normals of dist.sample() (models.py:114), (P*A, 2); NULL:
+     * drawn by the kernel from the native Philox stream */
+    const float *eps;
+    /* outputs */
+    float *actions;            /* (P, A, 2) policy scale (before ActionScaler) */
+    float *log_probs;          /* (P*A,)                                      */
+    float *values;             /* (P, 1)                                      */
+    float *eps_out;            /* optional (P*A, 2): the normals used         */
+} MarlnavPolicyBuffers;
+
+/* The forward-only policy work of one MAPPO.get_data step (models.py:113-120)
+ * in one launch: Actor.forward (models.py:27-36: fc1 WITHOUT an activation,
+ * mu = tanh(fc_mu), softplus(fc_std) used as the COVARIANCE diagonal of the
+ * MultivariateNormal), dist.sample() (:114) as mu + sqrt(v) * eps,
+ * dist.log_prob (:115) and Critic.forward (models.py:51-56, :120).
+ * eps NULL: the kernel draws the normals, keyed by (policy_seed, step_idx,
+ * global agent row (env_offset + e) * A + a), in a Philox block-index domain
+ * disjoint from the re-init draws of the same seed; the result does not
+ * depend on how envs are split into calls. With eps given, policy_seed and
+ * step_idx are not used. */
+int marlnav_policy_act(const MarlnavPolicyDims *dims, const MarlnavPolicyBuffers *bufs,
+                       uint64_t policy_seed, uint64_t step_idx, void *stream);
 
 /* Testing hook (not part of the reference's interface): restrict the step /
  * observe kernel selection to one family, process-wide. 0 = automatic (the

@@ -11,7 +11,7 @@ fallback: if the library is missing or fails to load, ``load_library`` raises.
 import ctypes
 import os
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 FRESH_STATES_FROM_MOVED = 0x1
 NOISY_AGENTS = 0x2
@@ -60,9 +60,31 @@ class MarlnavStepBuffers(ctypes.Structure):
     _fields_ = [(n, _P) for n in STEP_BUFFER_FIELDS]
 
 
+class MarlnavPolicyDims(ctypes.Structure):
+    _fields_ = [("num_parallel", ctypes.c_int64),
+                ("num_agents", ctypes.c_int32),
+                ("obs_dim", ctypes.c_int32),
+                ("hidden_size", ctypes.c_int32),
+                ("reserved", ctypes.c_int32),
+                ("env_offset", ctypes.c_int64)]
+
+
+POLICY_WEIGHT_FIELDS = (
+    "actor_fc1_w", "actor_fc1_b", "actor_mu_w", "actor_mu_b", "actor_std_w", "actor_std_b",
+    "critic_fc1_w", "critic_fc1_b", "critic_fc2_w", "critic_fc2_b")
+POLICY_BUFFER_FIELDS = (("obs_norm",) + POLICY_WEIGHT_FIELDS
+                        + ("eps", "actions", "log_probs", "values", "eps_out"))
+# every pointer but the two noise buffers must be given
+POLICY_REQUIRED_FIELDS = tuple(f for f in POLICY_BUFFER_FIELDS if f not in ("eps", "eps_out"))
+
+
+class MarlnavPolicyBuffers(ctypes.Structure):
+    _fields_ = [(n, _P) for n in POLICY_BUFFER_FIELDS]
+
+
 EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_formation_obs",
            "marlnav_counter_slots", "marlnav_counters_total",
-           "marlnav_returns_work_size", "marlnav_discounted_returns",
+           "marlnav_returns_work_size", "marlnav_discounted_returns", "marlnav_policy_act",
            "marlnav_last_error", "marlnav_abi_version",
            "marlnav_debug_force_family", "marlnav_debug_last_family",
            "marlnav_debug_acos_range", "marlnav_debug_fastdiv_check")
@@ -93,6 +115,9 @@ def _declare(lib):
     lib.marlnav_discounted_returns.argtypes = [_P, _P, c.c_int64, c.c_int64, c.c_double,
                                                _P, _P, _P, _P]
     lib.marlnav_discounted_returns.restype = c.c_int
+    lib.marlnav_policy_act.argtypes = [c.POINTER(MarlnavPolicyDims),
+                                       c.POINTER(MarlnavPolicyBuffers), c.c_uint64, c.c_uint64, _P]
+    lib.marlnav_policy_act.restype = c.c_int
     lib.marlnav_last_error.argtypes = []
     lib.marlnav_last_error.restype = c.c_char_p
     lib.marlnav_abi_version.argtypes = []

@@ -12,6 +12,13 @@ as one HIP scan instead of a Python loop of T x 3 small tensor ops.
   prints like the reference).
 * ``RolloutBuffer`` - preallocated stacked device storage for those six
   entries, so no per-step Python list growth and no stacking before the scan.
+* ``FusedPolicy(actor, critic)`` - the forward-only policy work of
+  ``MAPPO.get_data`` (models.py:113-120: ``Actor.forward``, the
+  ``MultivariateNormal``'s ``sample`` and ``log_prob``, ``Critic.forward``) as
+  one launch of libmarlnav.so ``marlnav_policy_act`` on the modules' live
+  parameter tensors.
+* ``collect(env, policy, buffer)`` - the ``get_data`` loop (models.py:106-125)
+  around ``Env.step`` with no ``torch.nn`` / ``torch.distributions`` call in it.
 
 Numerics: float64 like the reference (its accumulator is
 ``torch.zeros(P, dtype=float)``); the returns recursion is evaluated in the
@@ -108,6 +115,39 @@ class RolloutBuffer(object):
         self._n = 0
         self.returns = None
 
+    def reserve(self, num_parallel, num_agents, obs_dim, device):
+        """Allocate the storage for MAPPO.get_data's entry shapes (models.py:
+        113-121) without an ``add``: obs (P, A, D), actions (P, A, 2),
+        log_probs (P*A,), values (P, 1), rewards (P,), done (P,) bool. Keeps
+        storage that already has these shapes on ``device``."""
+        P, A, D = int(num_parallel), int(num_agents), int(obs_dim)
+        shapes = ((P, A, D), (P, A, 2), (P * A,), (P, 1), (P,), (P,))
+        dtypes = (torch.float32,) * 5 + (torch.bool,)
+        device = torch.device(device)
+        if self._store is not None and all(
+                tuple(s.shape[1:]) == sh and s.dtype == dt and s.device == device
+                for s, sh, dt in zip(self._store, shapes, dtypes)):
+            return
+        self._store = [torch.empty((self.buffer_len,) + sh, dtype=dt, device=device)
+                       for sh, dt in zip(shapes, dtypes)]
+        self.clear()
+
+    def row(self, t):
+        """The six storage rows of step ``t`` (views a producer writes in
+        place, in ``add``'s order); ``commit`` then makes them stored steps."""
+        if self._store is None:
+            raise RuntimeError("rollout buffer has no storage yet: reserve() or add() first")
+        if not 0 <= t < self.buffer_len:
+            raise IndexError(f"step {t} outside the rollout buffer ({self.buffer_len} steps)")
+        return tuple(s[t] for s in self._store)
+
+    def commit(self, n):
+        """Declare steps 0..n-1 stored (written through ``row``)."""
+        if not 0 <= n <= self.buffer_len:
+            raise IndexError(f"{n} steps do not fit the rollout buffer ({self.buffer_len})")
+        self._n = int(n)
+        self.returns = None
+
     def stacked(self, k):
         """Entry k (0..5) of every stored step, stacked: (n, ...)."""
         return self._store[k][:self._n]
@@ -130,3 +170,152 @@ class RolloutBuffer(object):
                 e[self.REWARDS] = self.returns[t]
             out.append(e)
         return out
+
+
+_POLICY_PARAMS = (("actor_fc1_w", "actor", "fc1", "weight"), ("actor_fc1_b", "actor", "fc1", "bias"),
+                  ("actor_mu_w", "actor", "fc_mu", "weight"), ("actor_mu_b", "actor", "fc_mu", "bias"),
+                  ("actor_std_w", "actor", "fc_std", "weight"),
+                  ("actor_std_b", "actor", "fc_std", "bias"),
+                  ("critic_fc1_w", "critic", "fc1", "weight"),
+                  ("critic_fc1_b", "critic", "fc1", "bias"),
+                  ("critic_fc2_w", "critic", "fc2", "weight"),
+                  ("critic_fc2_b", "critic", "fc2", "bias"))
+
+
+class FusedPolicy(object):
+    """``Actor`` + ``Critic`` (models.py:14-56) evaluated forward-only by one
+    HIP launch per call (include/marlnav.h ``marlnav_policy_act``).
+
+    ``actor`` / ``critic`` are any modules with the reference's attribute
+    names (``fc1``, ``fc_mu``, ``fc_std`` / ``fc1``, ``fc2``) and shapes.
+    Shapes, dtype (fp32), device and contiguity are checked here, once; the
+    kernel reads the parameter tensors themselves on every call (no copy is
+    kept), so an in-place optimiser step is seen by the next ``act``.
+
+    ``seed`` keys the kernel's own normals (``act`` without ``eps``);
+    ``env_offset`` is the global id of env 0 of this shard, so sharded runs
+    draw what the unsharded run draws for the same envs."""
+
+    def __init__(self, actor, critic, seed=0, env_offset=0):
+        self.actor, self.critic = actor, critic
+        mods = {"actor": actor, "critic": critic}
+        self._params = [(f, getattr(getattr(mods[m], layer), attr))
+                        for f, m, layer, attr in _POLICY_PARAMS]
+        p = dict(self._params)
+        dev = p["actor_fc1_w"].device
+        if dev.type != "cuda":
+            raise RuntimeError("FusedPolicy runs on a HIP device (no CPU fallback); "
+                               f"the actor's parameters are on {dev}")
+        for f, t in self._params:
+            if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"{f}: need a contiguous float32 tensor on {dev}, got "
+                                 f"{t.dtype} on {t.device}, contiguous={t.is_contiguous()}")
+        if p["actor_fc1_w"].dim() != 2:
+            raise ValueError("actor.fc1.weight must be (H, D)")
+        H, D = p["actor_fc1_w"].shape
+        AD = p["critic_fc1_w"].shape[1] if p["critic_fc1_w"].dim() == 2 else -1
+        want = {"actor_fc1_w": (H, D), "actor_fc1_b": (H,), "actor_mu_w": (2, H),
+                "actor_mu_b": (2,), "actor_std_w": (2, H), "actor_std_b": (2,),
+                "critic_fc1_w": (H, AD), "critic_fc1_b": (H,), "critic_fc2_w": (1, H),
+                "critic_fc2_b": (1,)}
+        for f, t in self._params:
+            if tuple(t.shape) != want[f]:
+                raise ValueError(f"{f}: shape {tuple(t.shape)}, expected {want[f]} "
+                                 "(one hidden size for both networks, models.py:69-70)")
+        if AD < 2 * D or AD % D:
+            raise ValueError(f"critic.fc1 takes {AD} inputs, not a multiple (>= 2) of the "
+                             f"actor's {D}")
+        self.device = dev
+        self.hidden_size, self.obs_dim, self.num_agents = int(H), int(D), int(AD // D)
+        self.seed = int(seed) & (2 ** 64 - 1)
+        self.step_idx = 0          # next step index of the kernel's own normals
+        self._lib = abi.load_library()
+        self._dims = abi.MarlnavPolicyDims(num_agents=self.num_agents, obs_dim=self.obs_dim,
+                                           hidden_size=self.hidden_size,
+                                           env_offset=int(env_offset))
+        self._bufs = abi.MarlnavPolicyBuffers()
+
+    def _check(self, t, shape, what):
+        if (t.dtype != torch.float32 or t.device != self.device or tuple(t.shape) != shape
+                or not t.is_contiguous()):
+            raise ValueError(f"{what}: need a contiguous float32 {shape} tensor on "
+                             f"{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t.data_ptr()
+
+    def act(self, obs_norm, eps=None, step_idx=None, out=None, eps_out=None):
+        """obs_norm (P, A, D) normalised observations -> (actions (P, A, 2) in
+        policy scale, log_probs (P*A,), values (P, 1)) as models.py:113-120
+        computes them. ``eps`` (P*A, 2): the standard normals to use (e.g.
+        ``torch.empty(P*A, 2).normal_()``, which is the reference's stream);
+        None: the kernel draws them for ``(seed, step_idx)`` (``step_idx``
+        None: this policy's running counter, which then advances). ``out``: a
+        triple of tensors to write into; ``eps_out`` (P*A, 2) receives the
+        normals used. One launch on the current stream, no synchronisation."""
+        if obs_norm.dim() != 3:
+            raise ValueError(f"obs_norm must be (P, A, D), got {tuple(obs_norm.shape)}")
+        P, A, D = int(obs_norm.shape[0]), self.num_agents, self.obs_dim
+        b, d = self._bufs, self._dims
+        b.obs_norm = self._check(obs_norm, (P, A, D), "obs_norm")
+        if out is None:
+            out = (torch.empty(P, A, 2, device=self.device),
+                   torch.empty(P * A, device=self.device),
+                   torch.empty(P, 1, device=self.device))
+        actions, log_probs, values = out
+        b.actions = self._check(actions, (P, A, 2), "out[0] (actions)")
+        b.log_probs = self._check(log_probs, (P * A,), "out[1] (log_probs)")
+        b.values = self._check(values, (P, 1), "out[2] (values)")
+        b.eps = None if eps is None else self._check(eps, (P * A, 2), "eps")
+        b.eps_out = None if eps_out is None else self._check(eps_out, (P * A, 2), "eps_out")
+        for f, t in self._params:
+            setattr(b, f, t.data_ptr())
+        if step_idx is None:
+            step_idx = self.step_idx
+            if eps is None:
+                self.step_idx += 1
+        d.num_parallel = P
+        abi.check(self._lib.marlnav_policy_act(ctypes.byref(d), ctypes.byref(b), self.seed,
+                                               int(step_idx), _stream(self.device)), self._lib)
+        return actions, log_probs, values
+
+
+def collect(env, policy, buffer, eps_source=None, gamma=0.9):
+    """MAPPO.get_data's loop (models.py:106-125) for ``buffer.buffer_len``
+    steps: the initial normalised observations, then per step ``policy.act``
+    straight into the buffer's row, ``env.step`` on those actions (the env's
+    attached ObsNormalizer and ActionScaler do the normalising and the
+    up-scaling inside the step kernel), ``done = terminated | truncated``;
+    after the loop ``_process_rewards`` (``buffer.process_rewards(gamma)``;
+    0.9 is the reference's default) and ``_update_epi_stats`` (the env's
+    episode counters are read and zeroed). Prints and file saving stay with
+    the caller.
+
+    ``eps_source(t)``: the (P*A, 2) standard normals of step ``t`` (None: the
+    kernel's own stream). Returns ``(mean_rew, {'trunc', 'col', 'tar'})``."""
+    nrm = env._normalizer
+    if nrm is None or env._action_scaler is None:
+        raise RuntimeError("collect needs env.attach_normalizer(...) and "
+                           "env.attach_action_scaler(...): the policy reads normalised "
+                           "observations and the env takes policy-scale actions")
+    P, A, D = env._obs_shape
+    if (A, D) != (policy.num_agents, policy.obs_dim):
+        raise ValueError(f"policy is built for {policy.num_agents} agents x {policy.obs_dim} "
+                         f"features, the env has {A} x {D}")
+    T = buffer.buffer_len
+    buffer.reserve(P, A, D, env.device)
+    buffer.clear()
+    obs_n = nrm(env.observations())        # models.py:110
+    for t in range(T):
+        o, actions, log_probs, values, rewards, done = buffer.row(t)
+        o.copy_(obs_n)
+        policy.act(obs_n, eps=None if eps_source is None else eps_source(t),
+                   out=(actions, log_probs, values))
+        obs, rew, terminated, truncated = env.step(actions)
+        torch.logical_or(terminated, truncated, out=done)
+        rewards.copy_(rew)
+        obs_n = nrm(obs)
+    buffer.commit(T)
+    mean = buffer.process_rewards(gamma)
+    trunc, col, tar = env._counter_totals()                # one read of the three counters
+    stats = {"trunc": trunc, "col": col, "tar": tar}
+    env._num_trunc = env._num_col = env._num_tar = 0      # models.py:153-158
+    return mean, stats

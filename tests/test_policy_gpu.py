@@ -1,0 +1,245 @@
+"""The fused policy step on the GPU (marlnav_policy_act through
+``FusedPolicy`` and ``collect``, marl-nav_amd/rollout.py) against fixture
+F6-policy and the torch restatement tests/policy_ref.py.
+
+Parity criterion (tests/policy_ref.py ``Pooled``): the reference's matmuls are
+MKL's, with an unspecified summation order, so bit-exactness cannot be asked.
+Both fp32 evaluations are measured against the fixture's fp64 values; per
+output kind and weight group, pooled over all cases, the kernel's largest
+absolute error must not exceed 4 x the reference's own largest fp32 error.
+The measured errors of both sides are printed to the terminal past pytest's
+capture (``capsys.disabled()``; tests/conftest.py owns the summary hook) and
+appended to the file named by MARLNAV_POLICY_PARITY_OUT, which is how
+profiles/policy_parity.txt was written."""
+import os
+from types import SimpleNamespace as NS
+
+import numpy as np
+import pytest
+import torch
+
+import policy_ref as pr
+import rng_stats
+from conftest import assert_bits_equal, cli_args
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+
+def np_(t):
+    return t.detach().cpu().numpy()
+
+
+def modules(w):
+    """Objects with the reference's attribute names around device tensors."""
+    lin = lambda p: NS(weight=w[p + ".weight"], bias=w[p + ".bias"])
+    return (NS(fc1=lin("actor.fc1"), fc_mu=lin("actor.fc_mu"), fc_std=lin("actor.fc_std")),
+            NS(fc1=lin("critic.fc1"), fc2=lin("critic.fc2")))
+
+
+def run_case(pkg, c, **kw):
+    w, obs, eps = pr.tensors(c, DEV)
+    policy = pkg.FusedPolicy(*modules(w), **kw)
+    return policy, w, obs, eps
+
+
+def report(capsys, title, pooled):
+    """The pooled errors of both sides, on the terminal whatever the capture
+    mode, and appended to $MARLNAV_POLICY_PARITY_OUT when that is set."""
+    text = "\n".join([f"{title} (largest |fp32 - fp64|, bound {pr.FACTOR:g} x reference)"]
+                     + ["  " + line for line in pooled.lines()])
+    with capsys.disabled():
+        print("\n" + text)
+    out = os.environ.get("MARLNAV_POLICY_PARITY_OUT")
+    if out:
+        with open(out, "a") as fh:
+            fh.write(text + "\n")
+
+
+def test_parity_with_supplied_eps(pkg, capsys):
+    pooled = pr.Pooled()
+    for name in pr.case_names():
+        for group in pr.GROUPS:
+            c = pr.load_case(name, group)
+            policy, w, obs, eps = run_case(pkg, c)
+            P, A = c["P"], c["A"]
+            eps_out = torch.empty(P * A, 2, device=DEV)
+            actions, log_probs, values = policy.act(obs, eps=eps, eps_out=eps_out)
+            assert actions.shape == (P, A, 2) and log_probs.shape == (P * A,)
+            assert values.shape == (P, 1)
+            assert_bits_equal(np_(eps_out), c["eps"], f"{name} eps_out")
+            pooled.add(c, [np_(actions), np_(log_probs), np_(values)])
+    report(capsys, "parity, supplied eps, every fixture case:", pooled)
+    assert not pooled.failures(), pooled.failures()
+
+
+def test_outputs_follow_in_place_weight_updates(pkg, capsys):
+    """The kernel reads the live parameter tensors: after an in-place update
+    the next call computes with the new weights (policy_ref on the updated
+    weights: fp64 as the truth, fp32 on the CPU as the reference side)."""
+    pooled = pr.Pooled()
+    for name in pr.case_names():
+        c = pr.load_case(name, "default")
+        policy, w, obs, eps = run_case(pkg, c)
+        before = [np_(o).copy() for o in policy.act(obs, eps=eps)]
+        for key, factor in (("actor.fc1.weight", 1.5), ("critic.fc1.weight", -0.75)):
+            w[key].mul_(factor)
+        after = [np_(o) for o in policy.act(obs, eps=eps)]
+        for b, a, kind in zip(before, after, pr.KINDS):
+            assert not np.array_equal(b, a), f"{name} {kind} did not follow the update"
+        w_cpu = {k: v.cpu() for k, v in w.items()}
+        ref32 = pr.policy_ref(w_cpu, obs.cpu(), eps.cpu())
+        ref64 = pr.policy_ref({k: v.double() for k, v in w_cpu.items()}, obs.cpu().double(),
+                              eps.cpu().double())
+        cc = {"name": name, "group": "default"}
+        for kind, r32, r64 in zip(pr.KINDS, ref32, ref64):
+            cc[kind], cc[kind + "64"] = r32.numpy(), r64.numpy()
+        pooled.add(cc, after)
+    report(capsys, "parity after in-place weight updates (default group only):", pooled)
+    assert not pooled.failures(), pooled.failures()
+
+
+# ------------------------------------------------------------------ native noise
+NP_, NA_ = 4096, 3
+
+
+@pytest.fixture(scope="module")
+def native(pkg):
+    """P = 4096 envs of 3 agents on the fixture's 3 x 3, H = 50 weights, the
+    kernel drawing its own normals: outputs and eps_out for (seed 11, step 5)."""
+    c = pr.load_case("p5a3o3h50", "default")
+    w, _, _ = pr.tensors(c, DEV)
+    gen = torch.Generator().manual_seed(99)
+    obs = (torch.rand(NP_, NA_, c["D"], generator=gen) * 2 - 1).to(DEV)
+
+    def act(seed, step, env_offset=0, rows=slice(None), eps=None):
+        policy = pkg.FusedPolicy(*modules(w), seed=seed, env_offset=env_offset)
+        o = obs[rows]
+        eps_out = torch.empty(o.shape[0] * NA_, 2, device=DEV)
+        out = policy.act(o, eps=eps, step_idx=step, eps_out=eps_out)
+        return [np_(x) for x in out] + [np_(eps_out)]
+
+    return NS(act=act, base=act(11, 5))
+
+
+def test_native_normals_have_the_standard_normal_law(native):
+    from scipy import stats
+    eps = native.base[3].astype(np.float64)
+    assert eps.shape == (NP_ * NA_, 2) and np.isfinite(eps).all()
+    n = eps.shape[0]
+    for comp in range(2):
+        z = eps[:, comp]
+        assert abs(z.mean()) < 6 / np.sqrt(n), (comp, z.mean())
+        assert abs(z.var() - 1.0) < 6 * np.sqrt(2.0 / n), (comp, z.var())
+        ks = stats.kstest(z, "norm")
+        assert ks.pvalue > rng_stats.P_MIN, (comp, ks)
+    rng_stats.check_uncorrelated(eps[:, 0], eps[:, 1], "policy eps components")
+    rng_stats.check_uncorrelated(eps[:-1, 0], eps[1:, 0], "policy eps row r, r+1")
+    ref = torch.randn(n, 2, generator=torch.Generator().manual_seed(7)).numpy()
+    rng_stats.check_same_law(eps, ref, "policy eps vs torch.randn")
+
+
+def test_native_noise_is_keyed_by_seed_and_step(native):
+    again = native.act(11, 5)
+    for a, b, what in zip(native.base, again, pr.KINDS + ("eps_out",)):
+        assert_bits_equal(a, b, f"same (seed, step): {what}")
+    for seed, step in ((12, 5), (11, 6), (11 + 2 ** 32, 5), (11, 5 + 2 ** 32)):
+        other = native.act(seed, step)
+        assert not np.array_equal(other[3], native.base[3]), (seed, step)
+        assert not np.array_equal(other[0], native.base[0]), (seed, step)
+        assert_bits_equal(other[2], native.base[2], "values do not depend on the noise")
+
+
+def test_eps_out_fed_back_reproduces_the_draw(native):
+    eps = torch.from_numpy(native.base[3]).to(DEV)
+    fed = native.act(0, 0, eps=eps)
+    assert_bits_equal(fed[0], native.base[0], "actions")
+    assert_bits_equal(fed[1], native.base[1], "log_probs")
+    assert_bits_equal(fed[3], native.base[3], "eps_out")
+
+
+def test_env_offset_slice_equals_the_full_batch(native):
+    lo, n = 1000, 77
+    part = native.act(11, 5, env_offset=lo, rows=slice(lo, lo + n))
+    assert_bits_equal(part[0], native.base[0][lo:lo + n], "actions")
+    assert_bits_equal(part[1], native.base[1][lo * NA_:(lo + n) * NA_], "log_probs")
+    assert_bits_equal(part[2], native.base[2][lo:lo + n], "values")
+    assert_bits_equal(part[3], native.base[3][lo * NA_:(lo + n) * NA_], "eps_out")
+    wrong = native.act(11, 5, env_offset=0, rows=slice(lo, lo + n))
+    assert not np.array_equal(wrong[3], part[3])
+
+
+# ------------------------------------------------------------------------ collect
+def _rollout_env(pkg, P, A, O):
+    args = cli_args(num_parallel=P, num_agents=A, num_obstacles=O, episode_len=5,
+                    risk_factor=2.0, distance_factor=3.0)
+    params = pkg.set_env_params(args, DEV)
+    params["rng"], params["seed"] = "native", 21
+    env = pkg.Env(params)
+    env.attach_normalizer(pkg.ObsNormalizer(pkg.set_normalizer_params(args, DEV)))
+    env.attach_action_scaler(pkg.ActionScaler(pkg.set_scaler_params(args, DEV)))
+    return env
+
+
+def test_collect_equals_the_loop_it_replaces(pkg, capsys):
+    """collect() against MAPPO.get_data's loop (models.py:106-125) written
+    out here with policy_ref on the device and buffer.add, on an identically
+    seeded second Env. The env half is bit-exact given equal actions, so the
+    loop's env is fed collect's recorded actions; the policy half is checked
+    per step under the parity criterion, pooled over the steps."""
+    P, A, O, T, gamma = 40, 3, 3, 12, 0.9
+    c = pr.load_case("p5a3o3h50", "default")
+    w, _, _ = pr.tensors(c, DEV)
+    eps_all = torch.randn(T, P * A, 2, generator=torch.Generator().manual_seed(3)).to(DEV)
+
+    env = _rollout_env(pkg, P, A, O)
+    policy = pkg.FusedPolicy(*modules(w))
+    buf = pkg.RolloutBuffer(T)
+    mean, stats = pkg.collect(env, policy, buf, eps_source=lambda t: eps_all[t], gamma=gamma)
+    assert len(buf) == T
+
+    env2 = _rollout_env(pkg, P, A, O)
+    nrm = env2._normalizer
+    buf2 = pkg.RolloutBuffer(T)
+    w64 = {k: v.double() for k, v in w.items()}
+    w_cpu = {k: v.cpu() for k, v in w.items()}
+    pooled = pr.Pooled()
+    obs_n = nrm(env2.observations())
+    for t in range(T):
+        got = [buf.stacked(k)[t] for k in range(6)]
+        assert_bits_equal(np_(got[0]), np_(obs_n), f"obs_norm {t}")
+        a_ref, lp_ref, v_ref = pr.policy_ref(w, obs_n, eps_all[t])
+        truth = pr.policy_ref(w64, obs_n.double(), eps_all[t].double())
+        ref32 = pr.policy_ref(w_cpu, obs_n.cpu(), eps_all[t].cpu())
+        cc = {"name": f"step{t}", "group": "default"}
+        for kind, r32, r64 in zip(pr.KINDS, ref32, truth):
+            cc[kind], cc[kind + "64"] = np_(r32), np_(r64)
+        pooled.add(cc, [np_(got[1]), np_(got[2]), np_(got[3])])
+        obs, rew, term, trunc = env2.step(got[1].clone())      # collect's recorded actions
+        done = torch.logical_or(term, trunc)
+        assert_bits_equal(np_(got[4]), np_(rew), f"reward {t}")
+        np.testing.assert_array_equal(np_(got[5]), np_(done), f"done {t}")
+        buf2.add(obs_n, a_ref, lp_ref, v_ref, rew, done)
+        obs_n = nrm(obs)
+    report(capsys, f"collect vs the written-out loop, {T} steps of {P} x {A} x {O}:", pooled)
+    assert not pooled.failures(), pooled.failures()
+    assert np_(buf.stacked(5)).any(), "no episode ended: the counters are not exercised"
+    mean2 = buf2.process_rewards(gamma)
+    np.testing.assert_array_equal(np_(buf.returns), np_(buf2.returns))
+    assert float(mean) == float(mean2)
+    assert stats == {"trunc": env2._num_trunc, "col": env2._num_col, "tar": env2._num_tar}
+    assert stats["trunc"] + stats["col"] + stats["tar"] > 0
+    assert (env._num_trunc, env._num_col, env._num_tar) == (0, 0, 0)   # models.py:156-158
+    for a, b in zip(buf.entries(), buf2.entries()):
+        np.testing.assert_array_equal(np_(a[4]), np_(b[4]))
+
+
+def test_act_checks_its_tensors(pkg):
+    c = pr.load_case("p5a3o3h50", "default")
+    policy, w, obs, eps = run_case(pkg, c)
+    with pytest.raises(ValueError, match="obs_norm"):
+        policy.act(obs[:, :2])
+    with pytest.raises(ValueError, match="eps"):
+        policy.act(obs, eps=eps[:-1])
+    with pytest.raises(ValueError, match="obs_norm"):
+        policy.act(obs.cpu())
