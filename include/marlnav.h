@@ -1,7 +1,7 @@
 /*
  * marlnav.h - C ABI of the MI355X (gfx950) environment-step library
  * (libmarlnav.so, built from marl-nav_amd/csrc/marlnav_step.hip,
- * marlnav_rollout.hip and marlnav_policy.hip).
+ * marlnav_rollout.hip, marlnav_policy.hip and marlnav_ppo.hip).
  *
  * The reference (JussiM01/MARL-nav) has no FFI: its boundary is the Python
  * class `Env` (marlnav/environment.py:8-286). Each entry point below replaces
@@ -247,6 +247,74 @@ typedef struct MarlnavPolicyBuffers {
  * step_idx are not used. */
 int marlnav_policy_act(const MarlnavPolicyDims *dims, const MarlnavPolicyBuffers *bufs,
                        uint64_t policy_seed, uint64_t step_idx, void *stream);
+
+/* Shapes of one PPO minibatch: rows lo..hi of a stacked rollout, T = hi - lo
+ * steps of P envs. N = T*P env rows, M = N*A agent rows in (t, p, a) order. */
+typedef struct MarlnavPpoDims {
+    int64_t num_parallel;    /* P  envs per step                              */
+    int64_t num_steps;       /* T  steps in the minibatch, >= 1, T*P >= 2     */
+    int32_t num_agents;      /* A  2 <= A <= 64                               */
+    int32_t obs_dim;         /* D  features per agent row                     */
+    int32_t hidden_size;     /* H  1 <= H <= 512                              */
+    int32_t reserved;        /* must be 0                                     */
+} MarlnavPpoDims;
+
+/* Device pointers of one PPO call, contiguous; fp32 unless noted. The data
+ * pointers address step `lo` of the stacked rollout storage; the ten weight
+ * pointers are the LIVE parameter tensors (nn.Linear layout), the ten
+ * gradient pointers their fp32 .grad tensors of the same shapes, which the
+ * call OVERWRITES (zero_grad() + backward()). */
+typedef struct MarlnavPpoBuffers {
+    const float *obs;          /* (T, P, A, D) normalised observations        */
+    const float *actions;      /* (T, P, A, 2) policy-scale actions           */
+    const float *log_probs;    /* (T, P*A) log-probs at collection time       */
+    const float *values;       /* (T, P) critic values at collection time     */
+    const double *returns;     /* (T, P) fp64 normalised returns              */
+    const float *actor_fc1_w;  /* weights as in MarlnavPolicyBuffers          */
+    const float *actor_fc1_b;
+    const float *actor_mu_w;
+    const float *actor_mu_b;
+    const float *actor_std_w;
+    const float *actor_std_b;
+    const float *critic_fc1_w;
+    const float *critic_fc1_b;
+    const float *critic_fc2_w;
+    const float *critic_fc2_b;
+    float *grad_actor_fc1_w;   /* gradients, the shapes of the weights        */
+    float *grad_actor_fc1_b;
+    float *grad_actor_mu_w;
+    float *grad_actor_mu_b;
+    float *grad_actor_std_w;
+    float *grad_actor_std_b;
+    float *grad_critic_fc1_w;
+    float *grad_critic_fc1_b;
+    float *grad_critic_fc2_w;
+    float *grad_critic_fc2_b;
+    double *loss;              /* 1 fp64 out                                  */
+    double *work;              /* marlnav_ppo_work_size(dims) fp64 scratch    */
+} MarlnavPpoBuffers;
+
+/* fp64 elements of MarlnavPpoBuffers.work for these dims (enough for either
+ * call); negative on bad dims. */
+int64_t marlnav_ppo_work_size(const MarlnavPpoDims *dims);
+
+/* MAPPO._actor_loss (models.py:270-299) of one minibatch and the gradient of
+ * every actor parameter, as zero_grad() + loss.backward() leave them
+ * (models.py:173-175). Quirks kept: softplus(fc_std) is the covariance
+ * diagonal; the advantage of agent row i is returns[i mod N] - values[i mod N]
+ * (the reference's repeat(num_agents) on the (t, p) vectors), in fp64; the
+ * clip bounds 1 -+ epsilon and ent_const act as fp32 scalars on fp32 tensors;
+ * the clipped mean is summed in fp64. Reads obs, actions, log_probs, values,
+ * returns, the six actor weights; writes the six actor gradients and loss.
+ * Fixed reduction order, no atomics: equal inputs give equal bits. */
+int marlnav_ppo_actor_grad(const MarlnavPpoDims *dims, const MarlnavPpoBuffers *bufs,
+                           double epsilon, double ent_const, void *stream);
+
+/* MAPPO._critic_loss (models.py:301-316) of one minibatch and the gradient of
+ * every critic parameter (models.py:193-195). Reads obs, values, returns, the
+ * four critic weights; writes the four critic gradients and loss. */
+int marlnav_ppo_critic_grad(const MarlnavPpoDims *dims, const MarlnavPpoBuffers *bufs,
+                            double epsilon, void *stream);
 
 /* Testing hook (not part of the reference's interface): restrict the step /
  * observe kernel selection to one family, process-wide. 0 = automatic (the

@@ -82,9 +82,35 @@ class MarlnavPolicyBuffers(ctypes.Structure):
     _fields_ = [(n, _P) for n in POLICY_BUFFER_FIELDS]
 
 
+class MarlnavPpoDims(ctypes.Structure):
+    _fields_ = [("num_parallel", ctypes.c_int64),
+                ("num_steps", ctypes.c_int64),
+                ("num_agents", ctypes.c_int32),
+                ("obs_dim", ctypes.c_int32),
+                ("hidden_size", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+PPO_DATA_FIELDS = ("obs", "actions", "log_probs", "values", "returns")
+PPO_GRAD_FIELDS = tuple("grad_" + f for f in POLICY_WEIGHT_FIELDS)
+PPO_BUFFER_FIELDS = PPO_DATA_FIELDS + POLICY_WEIGHT_FIELDS + PPO_GRAD_FIELDS + ("loss", "work")
+# what each call dereferences: its own network's weights and gradients only
+PPO_ACTOR_REQUIRED = (PPO_DATA_FIELDS
+                      + tuple(f for f in POLICY_WEIGHT_FIELDS + PPO_GRAD_FIELDS if "actor" in f)
+                      + ("loss", "work"))
+PPO_CRITIC_REQUIRED = (("obs", "values", "returns")
+                       + tuple(f for f in POLICY_WEIGHT_FIELDS + PPO_GRAD_FIELDS if "critic" in f)
+                       + ("loss", "work"))
+
+
+class MarlnavPpoBuffers(ctypes.Structure):
+    _fields_ = [(n, _P) for n in PPO_BUFFER_FIELDS]
+
+
 EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_formation_obs",
            "marlnav_counter_slots", "marlnav_counters_total",
            "marlnav_returns_work_size", "marlnav_discounted_returns", "marlnav_policy_act",
+           "marlnav_ppo_work_size", "marlnav_ppo_actor_grad", "marlnav_ppo_critic_grad",
            "marlnav_last_error", "marlnav_abi_version",
            "marlnav_debug_force_family", "marlnav_debug_last_family",
            "marlnav_debug_acos_range", "marlnav_debug_fastdiv_check")
@@ -118,6 +144,13 @@ def _declare(lib):
     lib.marlnav_policy_act.argtypes = [c.POINTER(MarlnavPolicyDims),
                                        c.POINTER(MarlnavPolicyBuffers), c.c_uint64, c.c_uint64, _P]
     lib.marlnav_policy_act.restype = c.c_int
+    ppo_dims_p, ppo_bufs_p = c.POINTER(MarlnavPpoDims), c.POINTER(MarlnavPpoBuffers)
+    lib.marlnav_ppo_work_size.argtypes = [ppo_dims_p]
+    lib.marlnav_ppo_work_size.restype = c.c_int64
+    lib.marlnav_ppo_actor_grad.argtypes = [ppo_dims_p, ppo_bufs_p, c.c_double, c.c_double, _P]
+    lib.marlnav_ppo_actor_grad.restype = c.c_int
+    lib.marlnav_ppo_critic_grad.argtypes = [ppo_dims_p, ppo_bufs_p, c.c_double, _P]
+    lib.marlnav_ppo_critic_grad.restype = c.c_int
     lib.marlnav_last_error.argtypes = []
     lib.marlnav_last_error.restype = c.c_char_p
     lib.marlnav_abi_version.argtypes = []

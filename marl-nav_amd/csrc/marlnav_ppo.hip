@@ -1,0 +1,913 @@
+// marlnav_ppo.hip - gfx950 kernels for the update half of the training loop:
+// MAPPO._actor_loss / _critic_loss (marlnav/models.py:270-316) of one
+// minibatch together with the gradient of every parameter, i.e. what
+// zero_grad() + loss.backward() leave in .grad (models.py:173-175, 193-195).
+// No autograd graph, no MultivariateNormal (a batched Cholesky per row in the
+// reference): the backward passes have closed forms.
+//
+// Shapes: T steps of P envs, N = T P env rows, M = N A agent rows in the
+// rollout buffer's (t, p, a) order, D features per agent row, H hidden units.
+//
+// Actor. fc1 has no activation, so pre = Weff x + beff with Weff = [Wmu;
+// Wstd] W1 (4 x D), as in marlnav_policy.hip. With g_i (4 values) the
+// gradient of the loss with respect to pre of row i, every parameter gradient
+// follows from S = sum_i g_i (x) [x_i, 1] = [S_x | s_1] (4 x (D + 1)):
+//   d[Wmu; Wstd] = S_x W1^T + s_1 b1^T    d[bmu; bstd] = s_1
+//   dW1 = [Wmu; Wstd]^T S_x               db1 = [Wmu; Wstd]^T s_1
+// actor_pass: a block owns a contiguous range of rows and walks it in tiles
+// of 256. Per tile, thread = row computes pre (4 D fp64 FMAs against Weff in
+// LDS, rounded to fp32), the loss terms and g (fp32, to LDS); then thread =
+// (column c of [x, 1], row slice) adds g_r x_rc over its rows of the tile into
+// four fp64 accumulators (the products of two fp32 are exact in fp64). Block
+// partials of S and of the two loss sums go to the workspace; actor_finish
+// (one block) adds them in block order and runs the epilogue above in fp64.
+//
+// Critic. h = relu(Wc x + bc), nv = w2 h + b2, delta_n = dloss/dnv_n;
+//   dWc = sum_n dh_n (x) x_n,  dh_nj = delta_n w2_j [h_nj > 0]   (H x A D)
+//   dbc = sum_n dh_n    dW2 = sum_n delta_n h_n    db2 = sum_n delta_n
+// critic_pass: grid = (row chunks, output tiles). A block walks its chunk in
+// tiles of 64 rows. Forward as in marlnav_policy.hip (lane = row, wave q sums
+// a quarter of the hidden units, weights through the scalar cache, fp32 FMA
+// chains of 64 inputs added up in fp64); h of the
+// block's own hidden units is kept in LDS, turned into dh once delta is
+// known, and thread = (column k, unit slice) adds dh_rj x_rk over the tile's
+// rows into JT fp64 accumulators (the ReLU prevents a collapse). Where the
+// output needs several tiles the forward pass runs once, in a launch of its
+// own on a finer row grid, and hands dh to the tiles' blocks through the
+// workspace instead of being recomputed per tile. critic_finish adds the
+// chunk partials per output element in chunk order.
+//
+// Determinism: no atomics, every sum in a fixed order that depends on the
+// dims only. Built with -ffp-contract=off: every FMA below is explicit.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/marlnav.h"
+
+__attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const char *msg);
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kMaxAgentsP = 64, kMaxObstP = 256, kMaxHidden = 512;
+constexpr int kMaxD = 2 * kMaxAgentsP + 2 * kMaxObstP;  // 640
+constexpr float kLog2Pi = 1.8378770664093453f;
+
+// ---- actor tiling
+constexpr int kActorTile = kThreads;       // rows per tile
+constexpr int kActorColsPerThread = 3;     // ceil((kMaxD + 1) / kThreads)
+constexpr int64_t kActorMaxBlocks = 1024;
+constexpr int64_t kActorMinRows = 1024;    // rows of a block, at least
+static_assert(kActorColsPerThread * kThreads >= kMaxD + 1, "columns of the widest row");
+
+// ---- critic tiling
+constexpr int kCriticTile = 64;            // rows per tile (lane = row)
+constexpr int kFwdChain = 64;              // inputs per fp32 FMA chain of the forward pass
+constexpr int64_t kCriticTargetBlocks = 512;
+constexpr int64_t kCriticMaxWork = 8 << 20;  // fp64 elements of chunk partials (64 MiB)
+constexpr int64_t kCriticForwardBlocks = 1024;
+
+struct PpoArgs {
+    MarlnavPpoBuffers b;
+    int64_t P, T, N, M;
+    int A, D, H;
+    int64_t rows_per_block;  // actor: rows of a block; critic: rows of a chunk
+    int64_t nblocks;         // actor: blocks; critic: chunks
+    // critic, forward pass shared through the workspace (else fw_part NULL):
+    // rows and count of the kForward blocks, their unit-vector partials
+    int64_t fw_rows, fw_blocks;
+    double *fw_part;         // [fw_blocks][2 H + 2]: dbc, dW2, db2, loss sum
+    float clip_lo, clip_hi, eps_f, ent_f;
+};
+
+__device__ __forceinline__ float relu_t(float a) { return a < 0.0f ? 0.0f : a; }  // NaN stays
+
+// wave partial sums (fixed shuffle tree), then the waves in order; valid in
+// thread 0. sh: kWaves doubles of LDS.
+__device__ __forceinline__ double block_sum(double v, double *sh)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) sh[w] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < kWaves; ++i) t += sh[i];
+    __syncthreads();
+    return t;
+}
+
+// p[0] + p[stride] + ... (n terms) in that order, the loads of eight terms
+// issued before their adds (a rolled loop pays one memory round trip per term)
+__device__ __forceinline__ double sum_strided(const double *__restrict__ p, int64_t n,
+                                              int64_t stride)
+{
+    double a = 0.0;
+    int64_t c = 0;
+    for (; c + 8 <= n; c += 8) {
+        double v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = p[(c + i) * stride];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a += v[i];
+    }
+    for (; c < n; ++c) a += p[c * stride];
+    return a;
+}
+
+// =========================================================================
+// actor
+// =========================================================================
+// LDS: Weff [D][4] and beff [4] in fp64, g [256][4] in fp32, kWaves doubles
+// of the block sums
+constexpr size_t actor_lds_bytes(int D)
+{
+    return sizeof(double) * ((size_t)4 * D + 4) + sizeof(float) * 4 * kActorTile +
+           sizeof(double) * kWaves;
+}
+static_assert(actor_lds_bytes(kMaxD) <= 64 * 1024, "LDS of the widest row");
+
+// workspace of the actor: per block 4 (D + 1) sums of S ([r][c], c == D the
+// ones column), then the surrogate sum and the entropy sum
+__device__ __host__ inline int64_t actor_stride(int D) { return 4 * (int64_t)(D + 1) + 2; }
+
+__global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g)
+{
+    const int D = g.D, H = g.H;
+    const int ncol = D + 1;
+    extern __shared__ __attribute__((aligned(16))) double s_dyn_d[];
+    double *s_w = s_dyn_d;              // Weff as [k][4]
+    double *s_b = s_w + 4 * D;          // beff
+    float *s_g = reinterpret_cast<float *>(s_b + 4);  // g of the tile's rows, [r][4]
+    double *s_red = reinterpret_cast<double *>(s_g + 4 * kActorTile);
+
+    const int t = threadIdx.x;
+    // ---- collapse: Weff[r][k] = sum_j head_r[j] W1[j][k], beff likewise. In
+    // fp64 (products of two fp32 are exact there), as is pre below: the new
+    // log-prob is subtracted from the stored one, so the rounding of pre is
+    // what the ratio's error is made of, and a row of 4 D FMAs is cheap
+    // beside its tanh / exp / log
+    for (int idx = t; idx < 4 * D + 4; idx += kThreads) {
+        const bool bias = idx >= 4 * D;
+        const int r = bias ? idx - 4 * D : idx / D;
+        const int k = bias ? 0 : idx - r * D;
+        const float *__restrict__ head = (r < 2 ? g.b.actor_mu_w : g.b.actor_std_w) + (r & 1) * H;
+        const float *__restrict__ col = bias ? g.b.actor_fc1_b : g.b.actor_fc1_w + k;
+        const int64_t stride = bias ? 1 : D;
+        double acc = 0.0;
+        for (int j = 0; j < H; j += 8) {  // the loads of a group before its FMAs
+            float a[8], b[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int jj = j + i < H ? j + i : H - 1;
+                a[i] = head[jj];
+                b[i] = col[jj * stride];
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                if (j + i < H) acc = __builtin_fma((double)a[i], (double)b[i], acc);
+        }
+        if (bias)
+            s_b[r] = (double)(r < 2 ? g.b.actor_mu_b : g.b.actor_std_b)[r & 1] + acc;
+        else
+            s_w[4 * k + r] = acc;
+    }
+    __syncthreads();
+
+    // phase-2 ownership: column(s) of [x, 1] and a slice of the tile's rows
+    const int slices = ncol >= kThreads ? 1 : kThreads / ncol;
+    const int us = ncol >= kThreads ? 0 : t / ncol;
+    const int kk = ncol >= kThreads ? t : t - us * ncol;
+    const bool own = us < slices;
+    double acc[kActorColsPerThread][4];
+#pragma unroll
+    for (int i = 0; i < kActorColsPerThread; ++i)
+        acc[i][0] = acc[i][1] = acc[i][2] = acc[i][3] = 0.0;
+    double sum_surr = 0.0, sum_ent = 0.0;
+
+    const int64_t M = g.M, N = g.N;
+    const double inv_m = 1.0 / (double)M;
+    const float ent_g = g.ent_f * 0.5f / (float)M;
+    const int64_t row_lo = (int64_t)blockIdx.x * g.rows_per_block;
+    const int64_t row_hi = row_lo + g.rows_per_block < M ? row_lo + g.rows_per_block : M;
+    const double be0 = s_b[0], be1 = s_b[1], be2 = s_b[2], be3 = s_b[3];
+
+    for (int64_t tile = row_lo; tile < row_hi; tile += kActorTile) {
+        // ---- phase 1: thread = row
+        const int64_t row = tile + t;
+        const int64_t tile_n = tile % N;  // wave-uniform: one scalar division per tile
+        float4 gr4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (row < row_hi) {
+            const float *__restrict__ xr = g.b.obs + row * D;
+            double a0 = be0, a1 = be1, a2 = be2, a3 = be3;
+            for (int k = 0; k < D; ++k) {
+                const double2 wa = *reinterpret_cast<const double2 *>(s_w + 4 * k);
+                const double2 wb = *reinterpret_cast<const double2 *>(s_w + 4 * k + 2);
+                const double xv = (double)xr[k];
+                a0 = __builtin_fma(wa.x, xv, a0);
+                a1 = __builtin_fma(wa.y, xv, a1);
+                a2 = __builtin_fma(wb.x, xv, a2);
+                a3 = __builtin_fma(wb.y, xv, a3);
+            }
+            const float p0 = (float)a0, p1 = (float)a1, p2 = (float)a2, p3 = (float)a3;
+            const float mu0 = tanhf(p0), mu1 = tanhf(p1);
+            const float v0 = p2 > 20.0f ? p2 : log1pf(expf(p2));
+            const float v1 = p3 > 20.0f ? p3 : log1pf(expf(p3));
+            const float d0 = g.b.actions[2 * row] - mu0, d1 = g.b.actions[2 * row + 1] - mu1;
+            const float iv0 = 1.0f / v0, iv1 = 1.0f / v1;
+            const float q0 = d0 * d0 * iv0, q1 = d1 * d1 * iv1;
+            const float ld = logf(v0) + logf(v1);
+            const float lp = __builtin_fmaf(-0.5f, q0 + q1, __builtin_fmaf(-0.5f, ld, -kLog2Pi));
+            const float ent = __builtin_fmaf(0.5f, ld, 1.0f + kLog2Pi);
+            const float ratio = expf(lp - g.b.log_probs[row]);
+            // row mod N: the reference's repeat(num_agents), not the row's env
+            int64_t n = tile_n + t;
+            if (n >= N) n = N >= kActorTile ? n - N : n % N;
+            const double adv = g.b.returns[n] - (double)g.b.values[n];
+            const float rc = ratio < g.clip_lo ? g.clip_lo : (ratio > g.clip_hi ? g.clip_hi : ratio);
+            const double sa = (double)ratio * adv, sb = (double)rc * adv;
+            sum_surr += sb < sa ? sb : sa;
+            sum_ent += (double)ent;
+            const bool inside = ratio >= g.clip_lo && ratio <= g.clip_hi;
+            const float g_ratio = (inside || sa < sb) ? (float)(adv * inv_m) : 0.0f;
+            const float g_lp = g_ratio * ratio;
+            const float g_mu0 = g_lp * (d0 * iv0), g_mu1 = g_lp * (d1 * iv1);
+            const float g_v0 = __builtin_fmaf(g_lp, 0.5f * iv0 * (q0 - 1.0f), ent_g * iv0);
+            const float g_v1 = __builtin_fmaf(g_lp, 0.5f * iv1 * (q1 - 1.0f), ent_g * iv1);
+            const float sg0 = p2 > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-p2));
+            const float sg1 = p3 > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-p3));
+            gr4.x = g_mu0 * __builtin_fmaf(-mu0, mu0, 1.0f);
+            gr4.y = g_mu1 * __builtin_fmaf(-mu1, mu1, 1.0f);
+            gr4.z = g_v0 * sg0;
+            gr4.w = g_v1 * sg1;
+        }
+        *reinterpret_cast<float4 *>(s_g + 4 * t) = gr4;  // rows past the end add zeros
+        __syncthreads();
+
+        // ---- phase 2: thread = (column, row slice); rows past the end hold g = 0
+        if (own) {
+            const int64_t left = row_hi - tile;
+            const int nrows = left < kActorTile ? (int)left : kActorTile;
+            for (int r = us; r < nrows; r += slices) {
+                const float4 gv = *reinterpret_cast<const float4 *>(s_g + 4 * r);
+                const float *__restrict__ xr = g.b.obs + (tile + r) * D;
+#pragma unroll
+                for (int i = 0; i < kActorColsPerThread; ++i) {
+                    const int c = kk + i * kThreads;
+                    if (c < ncol) {
+                        const double xv = c < D ? (double)xr[c] : 1.0;
+                        acc[i][0] = __builtin_fma((double)gv.x, xv, acc[i][0]);
+                        acc[i][1] = __builtin_fma((double)gv.y, xv, acc[i][1]);
+                        acc[i][2] = __builtin_fma((double)gv.z, xv, acc[i][2]);
+                        acc[i][3] = __builtin_fma((double)gv.w, xv, acc[i][3]);
+                    }
+                }
+            }
+        }
+        __syncthreads();  // s_g is rewritten by the next tile
+    }
+
+    // ---- block partials: the slices of a column added in slice order
+    double *__restrict__ out = g.b.work + (int64_t)blockIdx.x * actor_stride(D);
+    if (slices == 1) {
+        // 128 < ncol < 256: the threads t >= ncol own nothing (us == 1) and
+        // must not store their zeros over the owners' columns
+#pragma unroll
+        for (int i = 0; i < kActorColsPerThread; ++i) {
+            const int c = kk + i * kThreads;
+            if (own && c < ncol)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) out[r * ncol + c] = acc[i][r];
+        }
+    } else {
+        // through LDS in rounds of 4 values per thread (reusing s_g as fp64:
+        // 256 x 4 floats = 512 doubles = 2 values per thread and round)
+        double *s_acc = reinterpret_cast<double *>(s_g);
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            s_acc[2 * t] = acc[0][2 * half];
+            s_acc[2 * t + 1] = acc[0][2 * half + 1];
+            __syncthreads();
+            if (t < ncol) {
+                double a0 = 0.0, a1 = 0.0;
+                for (int s = 0; s < slices; ++s) {
+                    a0 += s_acc[2 * (s * ncol + t)];
+                    a1 += s_acc[2 * (s * ncol + t) + 1];
+                }
+                out[(2 * half) * ncol + t] = a0;
+                out[(2 * half + 1) * ncol + t] = a1;
+            }
+            __syncthreads();
+        }
+    }
+    const double bs = block_sum(sum_surr, s_red);
+    const double bent = block_sum(sum_ent, s_red);
+    if (t == 0) {
+        out[4 * ncol] = bs;
+        out[4 * ncol + 1] = bent;
+    }
+}
+
+// one block: S and the loss sums added over the blocks in block order, then
+// the epilogue. LDS: 4 (D + 1) + 2 doubles of totals, group partials before.
+__global__ void __launch_bounds__(kThreads) actor_finish(PpoArgs g)
+{
+    const int D = g.D, H = g.H, ncol = D + 1;
+    const int nS = 4 * ncol + 2;
+    extern __shared__ __attribute__((aligned(16))) double s_fin[];
+    double *s_S = s_fin;          // [r][c] totals, then the two loss sums
+    double *s_grp = s_fin + nS;   // group partials [grp][nS] when nS < kThreads
+    const int t = threadIdx.x;
+    const int64_t stride = actor_stride(D);
+    const double *__restrict__ work = g.b.work;
+    const int groups = nS >= kThreads ? 1 : kThreads / nS;
+    if (groups == 1) {
+        for (int c = t; c < nS; c += kThreads) s_S[c] = sum_strided(work + c, g.nblocks, stride);
+    } else {
+        const int grp = t / nS, c = t - grp * nS;
+        if (grp < groups) {
+            const int64_t n = grp < g.nblocks ? (g.nblocks - grp + groups - 1) / groups : 0;
+            s_grp[grp * nS + c] = sum_strided(work + grp * stride + c, n, groups * stride);
+        }
+        __syncthreads();
+        if (t < nS) {
+            double a = 0.0;
+            for (int q = 0; q < groups; ++q) a += s_grp[q * nS + t];
+            s_S[t] = a;
+        }
+    }
+    __syncthreads();
+
+    if (t == 0) {
+        // clip mean in fp64; entropy mean rounded to fp32 and scaled in fp32
+        const double clip_loss = s_S[4 * ncol] / (double)g.M;
+        const float ent_mean = (float)(s_S[4 * ncol + 1] / (double)g.M);
+        g.b.loss[0] = clip_loss + (double)(g.ent_f * ent_mean);
+    }
+    const double *S[4] = {s_S, s_S + ncol, s_S + 2 * ncol, s_S + 3 * ncol};
+    const float *__restrict__ w1 = g.b.actor_fc1_w;
+    const float *__restrict__ b1 = g.b.actor_fc1_b;
+    // d[Wmu; Wstd][r][j] = sum_k S_x[r][k] W1[j][k] + s_1[r] b1[j]
+    for (int idx = t; idx < 4 * H; idx += kThreads) {
+        const int r = idx / H, j = idx - r * H;
+        double a = S[r][D] * (double)b1[j];
+        for (int k = 0; k < D; ++k) a = __builtin_fma(S[r][k], (double)w1[(int64_t)j * D + k], a);
+        (r < 2 ? g.b.grad_actor_mu_w : g.b.grad_actor_std_w)[(r & 1) * H + j] = (float)a;
+    }
+    if (t < 4) (t < 2 ? g.b.grad_actor_mu_b : g.b.grad_actor_std_b)[t & 1] = (float)S[t][D];
+    // dW1[j][k] = sum_r head_r[j] S_x[r][k], db1[j] = sum_r head_r[j] s_1[r]
+    for (int64_t idx = t; idx < (int64_t)H * ncol; idx += kThreads) {
+        const int j = (int)(idx / ncol), c = (int)(idx - (int64_t)j * ncol);
+        double a = 0.0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float hw = (r < 2 ? g.b.actor_mu_w : g.b.actor_std_w)[(r & 1) * H + j];
+            a = __builtin_fma((double)hw, S[r][c], a);
+        }
+        if (c < D)
+            g.b.grad_actor_fc1_w[(int64_t)j * D + c] = (float)a;
+        else
+            g.b.grad_actor_fc1_b[j] = (float)a;
+    }
+}
+
+// =========================================================================
+// critic
+// =========================================================================
+// output tiling of one block: kc columns of A D (<= 256), `us_n` unit slices
+// of JT hidden units each
+struct CriticTiling {
+    int kc;        // columns of a column tile
+    int ncoltile;  // column tiles
+    int us_n;      // unit slices of a block
+    int ub;        // hidden units of a block = us_n * JT
+    int nugroup;   // unit groups
+    int jt;        // 8 or 64
+};
+
+inline CriticTiling critic_tiling(int AD, int H)
+{
+    CriticTiling c;
+    c.kc = AD < kThreads ? AD : kThreads;
+    c.ncoltile = (AD + c.kc - 1) / c.kc;
+    c.us_n = kThreads / c.kc;
+    // narrow rows: several unit slices of 8 share the block; wide rows: one
+    // slice of 64 (fewer blocks that recompute the forward pass)
+    c.jt = c.us_n >= 2 ? 8 : 64;
+    c.ub = c.us_n * c.jt;
+    if (c.ub > 64) {  // h of the block's units: at most 64 per row in LDS
+        c.us_n = 64 / c.jt;
+        c.ub = 64;
+    }
+    c.nugroup = (H + c.ub - 1) / c.ub;
+    return c;
+}
+
+// per-chunk workspace: dWc [H][AD], dbc [H], dW2 [H], db2, loss sum
+__device__ __host__ inline int64_t critic_stride(int AD, int H)
+{
+    return (int64_t)H * AD + 2 * (int64_t)H + 2;
+}
+
+constexpr int kHPad = 68;  // floats per row of the h tile: 64 units, rows 16-byte aligned
+constexpr size_t kCriticLdsBytes =
+    sizeof(float) * ((size_t)kCriticTile * kHPad + kWaves * kCriticTile + kCriticTile) +
+    sizeof(double) * (kWaves + 2 * kThreads);
+
+// MODE kFused: forward, delta, dh and the outer product in one block.
+// MODE kForward: everything but the outer product; dh of the block's units
+// goes to the workspace ([row][hp] fp32) for the kBackward blocks.
+// MODE kBackward: the outer product alone, dh read back from the workspace.
+enum { kFused = 0, kForward = 1, kBackward = 2 };
+
+template <int JT, int MODE>
+__global__ void __launch_bounds__(kThreads) critic_pass(PpoArgs g, CriticTiling ct, float *dhbuf,
+                                                         int hp, int vec4)
+{
+    const int A = g.A, D = g.D, H = g.H;
+    const int AD = A * D;
+    extern __shared__ __attribute__((aligned(16))) float s_dyn[];
+    float *s_h = s_dyn;                                // [row][kHPad]: h, then dh
+    float *s_part = s_h + kCriticTile * kHPad;         // [wave][row]
+    float *s_delta = s_part + kWaves * kCriticTile;    // [row]
+    double *s_red = reinterpret_cast<double *>(s_delta + kCriticTile);
+    double *s_vec = s_red + kWaves;                    // [2][256] unit-vector partials
+
+    const int t = threadIdx.x;
+    const int q = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int lane = t & 63;
+    const int Hq = (H + kWaves - 1) / kWaves;
+    const int j0 = q * Hq, j1 = (j0 + Hq < H) ? j0 + Hq : H;
+
+    const int coltile = blockIdx.y % ct.ncoltile, ugroup = blockIdx.y / ct.ncoltile;
+    const int ubase = ugroup * ct.ub;                   // first hidden unit of this block
+    const int col0 = coltile * ct.kc;
+    // phase-2 ownership
+    const int us = t / ct.kc, kk = t - us * ct.kc;
+    const int col = col0 + kk;
+    const bool own = us < ct.us_n && col < AD;
+    const int uj0 = us * JT;                            // first own unit, relative to ubase
+    double acc[JT];
+#pragma unroll
+    for (int i = 0; i < JT; ++i) acc[i] = 0.0;
+    // unit vectors dbc, dW2: thread = (unit jj = t & 63, row quarter t >> 6)
+    double a_bc = 0.0, a_w2 = 0.0, a_b2 = 0.0, a_loss = 0.0;
+    const bool first = blockIdx.y == 0;
+
+    const float *__restrict__ wc = g.b.critic_fc1_w;
+    const float *__restrict__ bc = g.b.critic_fc1_b;
+    const float *__restrict__ w2 = g.b.critic_fc2_w;
+    const float b2 = g.b.critic_fc2_b[0];
+    const int64_t N = g.N;
+    const double inv_n = 1.0 / (double)N;
+    const int64_t rows_blk = MODE == kForward ? g.fw_rows : g.rows_per_block;
+    const int64_t row_lo = (int64_t)blockIdx.x * rows_blk;
+    const int64_t row_hi = row_lo + rows_blk < N ? row_lo + rows_blk : N;
+
+    for (int64_t tile = row_lo; tile < row_hi; tile += kCriticTile) {
+        if constexpr (MODE == kBackward) {
+            // ---- dh of the tile's rows and the block's units, from the workspace
+            for (int idx = t; idx < kCriticTile * ct.ub; idx += kThreads) {
+                const int r = idx / ct.ub, jj = idx - r * ct.ub;
+                const int64_t row = tile + r;
+                const int j = ubase + jj;
+                s_h[r * kHPad + jj] = (row < row_hi && j < hp) ? dhbuf[row * hp + j] : 0.0f;
+            }
+        } else {
+            // ---- forward: wave q sums hidden units [j0, j1) for the tile's rows,
+            // eight units at a time (AD is even: D is; rows are 8-byte aligned, and
+            // 16-byte aligned where vec4 says so)
+            {
+                const int64_t row_raw = tile + lane;
+                const int64_t row = row_raw < row_hi ? row_raw : row_hi - 1;  // stays in bounds
+                const float *__restrict__ xe = g.b.obs + row * AD;
+                float part = 0.0f;
+                for (int j = j0; j < j1; j += 8) {
+                    // fp32 FMA chains of kFwdChain inputs, added up in fp64:
+                    // the rounding of a pre-activation does not grow with A D
+                    double d8[8];
+                    const float *wr[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const int jj = j + i < j1 ? j + i : j1 - 1;  // a short last group repeats a unit
+                        d8[i] = (double)bc[jj];
+                        wr[i] = wc + (int64_t)jj * AD;
+                    }
+                    for (int k0 = 0; k0 < AD; k0 += kFwdChain) {
+                        const int k1 = k0 + kFwdChain < AD ? k0 + kFwdChain : AD;
+                        float a8[8];
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) a8[i] = 0.0f;
+                        if (vec4) {
+                            for (int k = k0; k < k1; k += 4) {
+                                const float4 xv = *reinterpret_cast<const float4 *>(xe + k);
+#pragma unroll
+                                for (int i = 0; i < 8; ++i) {
+                                    a8[i] = __builtin_fmaf(wr[i][k], xv.x, a8[i]);
+                                    a8[i] = __builtin_fmaf(wr[i][k + 1], xv.y, a8[i]);
+                                    a8[i] = __builtin_fmaf(wr[i][k + 2], xv.z, a8[i]);
+                                    a8[i] = __builtin_fmaf(wr[i][k + 3], xv.w, a8[i]);
+                                }
+                            }
+                        } else {
+                            for (int k = k0; k < k1; k += 2) {
+                                const float2 xv = *reinterpret_cast<const float2 *>(xe + k);
+#pragma unroll
+                                for (int i = 0; i < 8; ++i) {
+                                    a8[i] = __builtin_fmaf(wr[i][k], xv.x, a8[i]);
+                                    a8[i] = __builtin_fmaf(wr[i][k + 1], xv.y, a8[i]);
+                                }
+                            }
+                        }
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) d8[i] += (double)a8[i];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 8; ++i)
+                        if (j + i < j1) {
+                            const float h = relu_t((float)d8[i]);
+                            part = __builtin_fmaf(w2[j + i], h, part);
+                            const int rel = j + i - ubase;
+                            if (rel >= 0 && rel < ct.ub) s_h[lane * kHPad + rel] = h;
+                        }
+                }
+                s_part[q * kCriticTile + lane] = part;
+            }
+            __syncthreads();
+            // ---- delta of the tile's rows
+            if (t < kCriticTile) {
+                const int64_t row = tile + t;
+                float delta = 0.0f;
+                if (row < row_hi) {
+                    float nv = s_part[t];
+#pragma unroll
+                    for (int w = 1; w < kWaves; ++w) nv += s_part[w * kCriticTile + t];
+                    nv += b2;
+                    const double ret = g.b.returns[row];
+                    const float val = g.b.values[row];
+                    const float lo = val - g.eps_f, hi = val + g.eps_f;
+                    const float cl = nv < lo ? lo : (nv > hi ? hi : nv);
+                    const double e0 = (double)nv - ret, e1 = (double)cl - ret;
+                    const double s0 = e0 * e0, s1 = e1 * e1;
+                    a_loss += s1 > s0 ? s1 : s0;
+                    const bool inside = nv >= lo && nv <= hi;
+                    const double gd = 2.0 * e0 * inv_n;
+                    // torch.maximum splits a tie; inside the clamp both halves arrive
+                    delta = inside || s0 > s1 ? (float)gd : (s0 == s1 ? (float)(0.5 * gd) : 0.0f);
+                    a_b2 += (double)delta;
+                }
+                s_delta[t] = delta;
+            }
+            __syncthreads();
+            // ---- h -> dh in place, with the unit vectors' sums
+            {
+                const int jj = lane, rq = q;
+                const int j = ubase + jj;
+                const bool unit = jj < ct.ub && j < H;
+                const float w2j = unit ? w2[j] : 0.0f;
+                for (int r = rq * 16; r < rq * 16 + 16; ++r) {
+                    const float dl = s_delta[r];
+                    float dh = 0.0f;
+                    if (unit && tile + r < row_hi) {  // padding rows repeat the last row
+                        const float h = s_h[r * kHPad + jj];
+                        a_w2 = __builtin_fma((double)dl, (double)h, a_w2);
+                        dh = h > 0.0f ? dl * w2j : 0.0f;
+                        a_bc += (double)dh;
+                    }
+                    if (jj < ct.ub) {
+                        if constexpr (MODE == kForward) {
+                            if (tile + r < row_hi) dhbuf[(tile + r) * hp + j] = dh;
+                        } else {
+                            s_h[r * kHPad + jj] = dh;  // units past H: zeros
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        // ---- outer product: thread = (column, unit slice)
+        if (MODE != kForward && own) {
+            const int64_t left = row_hi - tile;
+            const int nrows = left < kCriticTile ? (int)left : kCriticTile;
+            const float *__restrict__ xc = g.b.obs + tile * AD + col;
+            for (int r = 0; r < nrows; ++r) {
+                const double xv = (double)xc[(int64_t)r * AD];
+                // uj0 is a multiple of JT >= 8 floats, the row pitch of 16 bytes
+                const float4 *__restrict__ dh =
+                    reinterpret_cast<const float4 *>(s_h + r * kHPad + uj0);
+#pragma unroll
+                for (int i = 0; i < JT / 4; ++i) {
+                    const float4 d4 = dh[i];
+                    acc[4 * i] = __builtin_fma((double)d4.x, xv, acc[4 * i]);
+                    acc[4 * i + 1] = __builtin_fma((double)d4.y, xv, acc[4 * i + 1]);
+                    acc[4 * i + 2] = __builtin_fma((double)d4.z, xv, acc[4 * i + 2]);
+                    acc[4 * i + 3] = __builtin_fma((double)d4.w, xv, acc[4 * i + 3]);
+                }
+            }
+        }
+        __syncthreads();  // s_h, s_part, s_delta are rewritten by the next tile
+    }
+
+    double *__restrict__ out = g.b.work + (int64_t)blockIdx.x * critic_stride(AD, H);
+    if (MODE != kForward && own) {
+#pragma unroll
+        for (int i = 0; i < JT; ++i) {
+            const int j = ubase + uj0 + i;
+            if (j < H) out[(int64_t)j * AD + col] = acc[i];
+        }
+    }
+    if constexpr (MODE == kBackward) return;
+    double *__restrict__ vout = MODE == kForward
+                                    ? g.fw_part + (int64_t)blockIdx.x * (2 * H + 2)
+                                    : out + (int64_t)H * AD;
+    // unit vectors (the blocks of column tile 0), row quarters in order
+    if (coltile == 0) {
+        s_vec[t] = a_bc;
+        s_vec[kThreads + t] = a_w2;
+        __syncthreads();
+        if (t < ct.ub && ubase + t < H) {
+            double vb = 0.0, vw = 0.0;
+            for (int w = 0; w < kWaves; ++w) {
+                vb += s_vec[w * 64 + t];
+                vw += s_vec[kThreads + w * 64 + t];
+            }
+            vout[ubase + t] = vb;
+            vout[H + ubase + t] = vw;
+        }
+        __syncthreads();
+    }
+    if (first) {  // uniform per block
+        const double sb2 = block_sum(a_b2, s_red);
+        const double sl = block_sum(a_loss, s_red);
+        if (t == 0) {
+            vout[2 * H] = sb2;
+            vout[2 * H + 1] = sl;
+        }
+    }
+}
+
+// thread = output element: its chunk partials added in chunk order
+__global__ void __launch_bounds__(kThreads) critic_finish(PpoArgs g)
+{
+    const int H = g.H, AD = g.A * g.D;
+    const int64_t stride = critic_stride(AD, H);
+    const int64_t idx = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (idx >= stride) return;
+    const int64_t nW = (int64_t)H * AD;
+    double a = 0.0;
+    if (idx >= nW && g.fw_part) {  // the kForward blocks' partials
+        a = sum_strided(g.fw_part + (idx - nW), g.fw_blocks, 2 * H + 2);
+    } else {
+        a = sum_strided(g.b.work + idx, g.nblocks, stride);
+    }
+    if (idx < nW)
+        g.b.grad_critic_fc1_w[idx] = (float)a;
+    else if (idx < nW + H)
+        g.b.grad_critic_fc1_b[idx - nW] = (float)a;
+    else if (idx < nW + 2 * H)
+        g.b.grad_critic_fc2_w[idx - nW - H] = (float)a;
+    else if (idx == nW + 2 * H)
+        g.b.grad_critic_fc2_b[0] = (float)a;
+    else
+        g.b.loss[0] = a / (double)g.N;
+}
+
+// ---- host side
+int failf(int code, const char *fmt, long long a, long long b, long long c)
+{
+    char msg[256];
+    snprintf(msg, sizeof(msg), fmt, a, b, c);
+    return marlnav_internal_fail(code, msg);
+}
+
+int check_dims(const MarlnavPpoDims *d)
+{
+    if (!d) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo dims is NULL");
+    if (d->num_parallel < 1)
+        return failf(MARLNAV_EINVAL, "ppo: num_parallel=%lld < 1", d->num_parallel, 0, 0);
+    if (d->num_steps < 1)
+        return failf(MARLNAV_EINVAL, "ppo: num_steps=%lld < 1", d->num_steps, 0, 0);
+    if (d->num_agents < 2 || d->num_agents > kMaxAgentsP)
+        return failf(MARLNAV_EINVAL, "ppo: num_agents=%lld outside [2, %lld]", d->num_agents,
+                     kMaxAgentsP, 0);
+    if (d->hidden_size < 1 || d->hidden_size > kMaxHidden)
+        return failf(MARLNAV_EINVAL, "ppo: hidden_size=%lld outside [1, %lld]", d->hidden_size,
+                     kMaxHidden, 0);
+    const int twoO = d->obs_dim - 2 * d->num_agents;
+    if (twoO < 2 || (twoO & 1) || twoO > 2 * kMaxObstP)
+        return failf(MARLNAV_EINVAL,
+                     "ppo: obs_dim=%lld is not 2 + 2*O + 2*(A-1) for num_agents=%lld and an O in "
+                     "[1, %lld]",
+                     d->obs_dim, d->num_agents, kMaxObstP);
+    if (d->reserved != 0) return failf(MARLNAV_EINVAL, "ppo: reserved=%lld must be 0", d->reserved, 0, 0);
+    if (d->num_steps > ((int64_t)1 << 40) / d->num_parallel / d->num_agents)
+        return failf(MARLNAV_EINVAL, "ppo: num_steps=%lld x num_parallel=%lld rows are too many",
+                     d->num_steps, d->num_parallel, 0);
+    if (d->num_steps * d->num_parallel < 2)
+        return failf(MARLNAV_EINVAL,
+                     "ppo: num_steps=%lld x num_parallel=%lld gives fewer than 2 env rows",
+                     d->num_steps, d->num_parallel, 0);
+    return 0;
+}
+
+void actor_grid(int64_t M, int64_t &rows_per_block, int64_t &nblocks)
+{
+    int64_t rows = (M + kActorMaxBlocks - 1) / kActorMaxBlocks;
+    if (rows < kActorMinRows) rows = kActorMinRows;
+    rows = (rows + kActorTile - 1) / kActorTile * kActorTile;
+    rows_per_block = rows;
+    nblocks = (M + rows - 1) / rows;
+}
+
+void critic_grid(int64_t N, int AD, int H, const CriticTiling &ct, int64_t &rows_per_chunk,
+                 int64_t &nchunks)
+{
+    const int64_t per_y = (int64_t)ct.ncoltile * ct.nugroup;
+    int64_t want = kCriticTargetBlocks / per_y;
+    const int64_t fit = kCriticMaxWork / critic_stride(AD, H);
+    if (want > fit) want = fit;
+    if (want < 1) want = 1;
+    const int64_t tiles = (N + kCriticTile - 1) / kCriticTile;
+    const int64_t tiles_per_chunk = (tiles + want - 1) / want;
+    rows_per_chunk = tiles_per_chunk * kCriticTile;
+    nchunks = (N + rows_per_chunk - 1) / rows_per_chunk;
+}
+
+// The forward pass is shared through the workspace (kForward + kBackward
+// launches) where the fused kernel would recompute it in several output
+// tiles and dh of the whole minibatch ([N][hp] fp32) stays within bounds.
+constexpr int64_t kCriticMaxDh = 32 << 20;  // floats (128 MiB)
+
+inline int dh_pitch(int H) { return (H + 63) / 64 * 64; }
+
+inline bool critic_split(int64_t N, int H, const CriticTiling &ct)
+{
+    return ct.ncoltile * ct.nugroup > 1 && N * dh_pitch(H) <= kCriticMaxDh;
+}
+
+// rows and count of the kForward blocks (finer than the chunks: they write
+// 2 H + 2 partial sums each, not an H x A D tile)
+inline void critic_forward_grid(int64_t N, int64_t &rows, int64_t &nblocks)
+{
+    rows = (N + kCriticForwardBlocks - 1) / kCriticForwardBlocks;
+    rows = (rows + kCriticTile - 1) / kCriticTile * kCriticTile;
+    nblocks = (N + rows - 1) / rows;
+}
+
+PpoArgs make_args(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b)
+{
+    PpoArgs a;
+    a.b = *b;
+    a.P = d->num_parallel;
+    a.T = d->num_steps;
+    a.N = a.T * a.P;
+    a.A = d->num_agents;
+    a.M = a.N * a.A;
+    a.D = d->obs_dim;
+    a.H = d->hidden_size;
+    a.rows_per_block = a.nblocks = 0;
+    a.fw_rows = a.fw_blocks = 0;
+    a.fw_part = nullptr;
+    a.clip_lo = a.clip_hi = a.eps_f = a.ent_f = 0.0f;
+    return a;
+}
+
+#define PPO_NEED(field)                                                                   \
+    if (!b->field) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer " #field " is NULL")
+
+}  // namespace
+
+extern "C" int64_t marlnav_ppo_work_size(const MarlnavPpoDims *d)
+{
+    const int rc = check_dims(d);
+    if (rc) return rc;
+    const int64_t N = d->num_steps * d->num_parallel, M = N * d->num_agents;
+    int64_t rows, nb;
+    actor_grid(M, rows, nb);
+    const int64_t actor = nb * actor_stride(d->obs_dim);
+    const int AD = d->num_agents * d->obs_dim;
+    const CriticTiling ct = critic_tiling(AD, d->hidden_size);
+    critic_grid(N, AD, d->hidden_size, ct, rows, nb);
+    int64_t critic = nb * critic_stride(AD, d->hidden_size);
+    if (critic_split(N, d->hidden_size, ct)) {
+        int64_t fr, fb;
+        critic_forward_grid(N, fr, fb);
+        critic += fb * (2 * d->hidden_size + 2) + (N * dh_pitch(d->hidden_size) + 1) / 2;
+    }
+    return actor > critic ? actor : critic;
+}
+
+extern "C" int marlnav_ppo_actor_grad(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                                      double epsilon, double ent_const, void *stream)
+{
+    const int rc = check_dims(d);
+    if (rc) return rc;
+    if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
+    PPO_NEED(obs);
+    PPO_NEED(actions);
+    PPO_NEED(log_probs);
+    PPO_NEED(values);
+    PPO_NEED(returns);
+    PPO_NEED(actor_fc1_w);
+    PPO_NEED(actor_fc1_b);
+    PPO_NEED(actor_mu_w);
+    PPO_NEED(actor_mu_b);
+    PPO_NEED(actor_std_w);
+    PPO_NEED(actor_std_b);
+    PPO_NEED(grad_actor_fc1_w);
+    PPO_NEED(grad_actor_fc1_b);
+    PPO_NEED(grad_actor_mu_w);
+    PPO_NEED(grad_actor_mu_b);
+    PPO_NEED(grad_actor_std_w);
+    PPO_NEED(grad_actor_std_b);
+    PPO_NEED(loss);
+    PPO_NEED(work);
+
+    PpoArgs a = make_args(d, b);
+    actor_grid(a.M, a.rows_per_block, a.nblocks);
+    // the reference's Python scalars 1 - margin, 1 + margin and ent_const meet
+    // fp32 tensors: rounded to fp32 once
+    a.clip_lo = (float)(1.0 - epsilon);
+    a.clip_hi = (float)(1.0 + epsilon);
+    a.ent_f = (float)ent_const;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(actor_pass, dim3((unsigned)a.nblocks), dim3(kThreads),
+                       actor_lds_bytes(a.D), s, a);
+    const int nS = 4 * (a.D + 1) + 2;
+    const int groups = nS >= kThreads ? 1 : kThreads / nS;
+    const size_t fin_lds = sizeof(double) * (size_t)nS * (1 + (groups > 1 ? groups : 0));
+    hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), fin_lds, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int marlnav_ppo_critic_grad(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                                       double epsilon, void *stream)
+{
+    const int rc = check_dims(d);
+    if (rc) return rc;
+    if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
+    PPO_NEED(obs);
+    PPO_NEED(values);
+    PPO_NEED(returns);
+    PPO_NEED(critic_fc1_w);
+    PPO_NEED(critic_fc1_b);
+    PPO_NEED(critic_fc2_w);
+    PPO_NEED(critic_fc2_b);
+    PPO_NEED(grad_critic_fc1_w);
+    PPO_NEED(grad_critic_fc1_b);
+    PPO_NEED(grad_critic_fc2_w);
+    PPO_NEED(grad_critic_fc2_b);
+    PPO_NEED(loss);
+    PPO_NEED(work);
+    if (reinterpret_cast<uintptr_t>(b->obs) & 7u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer obs must be 8-byte aligned");
+
+    PpoArgs a = make_args(d, b);
+    const int AD = a.A * a.D;
+    const CriticTiling ct = critic_tiling(AD, a.H);
+    critic_grid(a.N, AD, a.H, ct, a.rows_per_block, a.nblocks);
+    a.eps_f = (float)epsilon;  // values - epsilon: a Python scalar against an fp32 tensor
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)a.nblocks, (unsigned)(ct.ncoltile * ct.nugroup));
+    const int vec4 = AD % 4 == 0 && (reinterpret_cast<uintptr_t>(b->obs) & 15u) == 0;
+    if (critic_split(a.N, a.H, ct)) {
+        // forward once per row: blocks of 64 hidden units, no output tile
+        CriticTiling fw = ct;
+        fw.kc = AD < kThreads ? AD : kThreads;
+        fw.ncoltile = 1;
+        fw.us_n = 1;
+        fw.jt = 64;
+        fw.ub = 64;
+        fw.nugroup = (a.H + 63) / 64;
+        const int hp = dh_pitch(a.H);
+        critic_forward_grid(a.N, a.fw_rows, a.fw_blocks);
+        a.fw_part = b->work + a.nblocks * critic_stride(AD, a.H);
+        float *dhbuf = reinterpret_cast<float *>(a.fw_part + a.fw_blocks * (2 * a.H + 2));
+        hipLaunchKernelGGL((critic_pass<1, kForward>),
+                           dim3((unsigned)a.fw_blocks, (unsigned)fw.nugroup), dim3(kThreads),
+                           kCriticLdsBytes, s, a, fw, dhbuf, hp, vec4);
+        if (ct.jt == 8)
+            hipLaunchKernelGGL((critic_pass<8, kBackward>), grid, dim3(kThreads), kCriticLdsBytes,
+                               s, a, ct, dhbuf, hp, vec4);
+        else
+            hipLaunchKernelGGL((critic_pass<64, kBackward>), grid, dim3(kThreads), kCriticLdsBytes,
+                               s, a, ct, dhbuf, hp, vec4);
+    } else if (ct.jt == 8) {
+        hipLaunchKernelGGL((critic_pass<8, kFused>), grid, dim3(kThreads), kCriticLdsBytes, s, a, ct,
+                           (float *)nullptr, 0, vec4);
+    } else {
+        hipLaunchKernelGGL((critic_pass<64, kFused>), grid, dim3(kThreads), kCriticLdsBytes, s, a,
+                           ct, (float *)nullptr, 0, vec4);
+    }
+    const int64_t nout = critic_stride(AD, a.H);
+    hipLaunchKernelGGL(critic_finish, dim3((unsigned)((nout + kThreads - 1) / kThreads)),
+                       dim3(kThreads), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
+    return 0;
+}

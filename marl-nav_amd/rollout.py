@@ -19,6 +19,12 @@ as one HIP scan instead of a Python loop of T x 3 small tensor ops.
   parameter tensors.
 * ``collect(env, policy, buffer)`` - the ``get_data`` loop (models.py:106-125)
   around ``Env.step`` with no ``torch.nn`` / ``torch.distributions`` call in it.
+* ``FusedPPO(actor, critic, epsilon, ent_const)`` - ``MAPPO._actor_loss`` /
+  ``_critic_loss`` (models.py:270-316) of one minibatch with the gradient of
+  every parameter written to ``.grad`` (libmarlnav.so
+  ``marlnav_ppo_actor_grad`` / ``marlnav_ppo_critic_grad``), and
+  ``train_actor`` / ``train_critic`` / ``minibatch_bounds``, the loops of
+  models.py:160-198 around them and the caller's ``torch.optim`` optimiser.
 
 Numerics: float64 like the reference (its accumulator is
 ``torch.zeros(P, dtype=float)``); the returns recursion is evaluated in the
@@ -182,6 +188,40 @@ _POLICY_PARAMS = (("actor_fc1_w", "actor", "fc1", "weight"), ("actor_fc1_b", "ac
                   ("critic_fc2_b", "critic", "fc2", "bias"))
 
 
+def _module_params(actor, critic, who):
+    """The ten live parameter tensors of ``actor`` / ``critic`` as
+    ``[(field, tensor)]`` in ``_POLICY_PARAMS`` order, checked once (fp32,
+    one HIP device, contiguous, the reference's shapes); -> (params, device,
+    H, D, A)."""
+    mods = {"actor": actor, "critic": critic}
+    params = [(f, getattr(getattr(mods[m], layer), attr)) for f, m, layer, attr in _POLICY_PARAMS]
+    p = dict(params)
+    dev = p["actor_fc1_w"].device
+    if dev.type != "cuda":
+        raise RuntimeError(f"{who} runs on a HIP device (no CPU fallback); "
+                           f"the actor's parameters are on {dev}")
+    for f, t in params:
+        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{f}: need a contiguous float32 tensor on {dev}, got "
+                             f"{t.dtype} on {t.device}, contiguous={t.is_contiguous()}")
+    if p["actor_fc1_w"].dim() != 2:
+        raise ValueError("actor.fc1.weight must be (H, D)")
+    H, D = p["actor_fc1_w"].shape
+    AD = p["critic_fc1_w"].shape[1] if p["critic_fc1_w"].dim() == 2 else -1
+    want = {"actor_fc1_w": (H, D), "actor_fc1_b": (H,), "actor_mu_w": (2, H),
+            "actor_mu_b": (2,), "actor_std_w": (2, H), "actor_std_b": (2,),
+            "critic_fc1_w": (H, AD), "critic_fc1_b": (H,), "critic_fc2_w": (1, H),
+            "critic_fc2_b": (1,)}
+    for f, t in params:
+        if tuple(t.shape) != want[f]:
+            raise ValueError(f"{f}: shape {tuple(t.shape)}, expected {want[f]} "
+                             "(one hidden size for both networks, models.py:69-70)")
+    if AD < 2 * D or AD % D:
+        raise ValueError(f"critic.fc1 takes {AD} inputs, not a multiple (>= 2) of the "
+                         f"actor's {D}")
+    return params, dev, int(H), int(D), int(AD // D)
+
+
 class FusedPolicy(object):
     """``Actor`` + ``Critic`` (models.py:14-56) evaluated forward-only by one
     HIP launch per call (include/marlnav.h ``marlnav_policy_act``).
@@ -198,35 +238,8 @@ class FusedPolicy(object):
 
     def __init__(self, actor, critic, seed=0, env_offset=0):
         self.actor, self.critic = actor, critic
-        mods = {"actor": actor, "critic": critic}
-        self._params = [(f, getattr(getattr(mods[m], layer), attr))
-                        for f, m, layer, attr in _POLICY_PARAMS]
-        p = dict(self._params)
-        dev = p["actor_fc1_w"].device
-        if dev.type != "cuda":
-            raise RuntimeError("FusedPolicy runs on a HIP device (no CPU fallback); "
-                               f"the actor's parameters are on {dev}")
-        for f, t in self._params:
-            if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
-                raise ValueError(f"{f}: need a contiguous float32 tensor on {dev}, got "
-                                 f"{t.dtype} on {t.device}, contiguous={t.is_contiguous()}")
-        if p["actor_fc1_w"].dim() != 2:
-            raise ValueError("actor.fc1.weight must be (H, D)")
-        H, D = p["actor_fc1_w"].shape
-        AD = p["critic_fc1_w"].shape[1] if p["critic_fc1_w"].dim() == 2 else -1
-        want = {"actor_fc1_w": (H, D), "actor_fc1_b": (H,), "actor_mu_w": (2, H),
-                "actor_mu_b": (2,), "actor_std_w": (2, H), "actor_std_b": (2,),
-                "critic_fc1_w": (H, AD), "critic_fc1_b": (H,), "critic_fc2_w": (1, H),
-                "critic_fc2_b": (1,)}
-        for f, t in self._params:
-            if tuple(t.shape) != want[f]:
-                raise ValueError(f"{f}: shape {tuple(t.shape)}, expected {want[f]} "
-                                 "(one hidden size for both networks, models.py:69-70)")
-        if AD < 2 * D or AD % D:
-            raise ValueError(f"critic.fc1 takes {AD} inputs, not a multiple (>= 2) of the "
-                             f"actor's {D}")
-        self.device = dev
-        self.hidden_size, self.obs_dim, self.num_agents = int(H), int(D), int(AD // D)
+        self._params, self.device, H, D, A = _module_params(actor, critic, "FusedPolicy")
+        self.hidden_size, self.obs_dim, self.num_agents = H, D, A
         self.seed = int(seed) & (2 ** 64 - 1)
         self.step_idx = 0          # next step index of the kernel's own normals
         self._lib = abi.load_library()
@@ -319,3 +332,147 @@ def collect(env, policy, buffer, eps_source=None, gamma=0.9):
     stats = {"trunc": trunc, "col": col, "tar": tar}
     env._num_trunc = env._num_col = env._num_tar = 0      # models.py:153-158
     return mean, stats
+
+
+def minibatch_bounds(buffer_len, batch_size):
+    """The minibatch slices of MAPPO.train_actor / train_critic (models.py:
+    165-172) as ``[(lo, hi)]`` step ranges: ``buffer_len // batch_size`` of
+    them, ``[start : start + batch_size]`` while ``start + batch_size <
+    buffer_len``, else ``[start : -1]`` - the last batch loses the buffer's
+    final step. An empty slice (where the reference's ``torch.cat`` raises) is
+    a ValueError."""
+    buffer_len, batch_size = int(buffer_len), int(batch_size)
+    if batch_size < 1 or buffer_len < 1:
+        raise ValueError(f"buffer_len={buffer_len} and batch_size={batch_size} must be >= 1")
+    out = []
+    for j in range(buffer_len // batch_size):
+        lo = j * batch_size
+        hi = lo + batch_size if lo + batch_size < buffer_len else buffer_len - 1
+        if hi <= lo:
+            raise ValueError(f"minibatch {j} of buffer_len={buffer_len}, batch_size={batch_size} "
+                             f"is the empty slice [{lo}:-1]")
+        out.append((lo, hi))
+    return out
+
+
+class FusedPPO(object):
+    """``MAPPO._actor_loss`` / ``_critic_loss`` (models.py:270-316) of one
+    minibatch with ``zero_grad()`` + ``backward()`` (models.py:173-175,
+    193-195), by libmarlnav.so ``marlnav_ppo_actor_grad`` /
+    ``marlnav_ppo_critic_grad``: no autograd graph and no
+    ``MultivariateNormal``. The kernels read steps ``lo..hi`` of a
+    ``RolloutBuffer``'s stacked storage in place and the modules' live
+    parameter tensors, and OVERWRITE the parameters' ``.grad`` (allocated here
+    where None), so a ``torch.optim`` optimiser's ``step()`` follows directly.
+
+    ``actor`` / ``critic``: checked as ``FusedPolicy`` checks them. ``epsilon``
+    and ``ent_const`` are the reference's Python scalars.
+
+    Single device: the losses are means over the whole minibatch and the
+    advantage of agent row ``i`` is that of env row ``i mod (T*P)`` (the
+    reference's ``repeat(num_agents)``, kept), which pairs rows across env
+    shards; training over ``shard``-split envs needs an all-reduce of the
+    gradients and a cross-shard reading of that pairing, neither of which is
+    here."""
+
+    def __init__(self, actor, critic, epsilon, ent_const):
+        self.actor, self.critic = actor, critic
+        self._params, self.device, H, D, A = _module_params(actor, critic, "FusedPPO")
+        self.hidden_size, self.obs_dim, self.num_agents = H, D, A
+        self.epsilon, self.ent_const = float(epsilon), float(ent_const)
+        self._lib = abi.load_library()
+        self._dims = abi.MarlnavPpoDims(num_agents=A, obs_dim=D, hidden_size=H)
+        self._bufs = abi.MarlnavPpoBuffers()
+        self._work = None
+        for f, t in self._params:
+            if t.grad is None:
+                t.grad = torch.zeros_like(t)
+
+    def _bind(self, buffer, lo, hi):
+        """Point the call's structs at steps lo..hi of the buffer; -> loss."""
+        if buffer.returns is None:
+            raise RuntimeError("the rollout buffer has no returns yet: call "
+                               "buffer.process_rewards(gamma) (or collect()) before training")
+        n = len(buffer)
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi <= n:
+            raise ValueError(f"steps [{lo}:{hi}] are not a non-empty range of the {n} stored steps")
+        obs, actions, log_probs, values = (buffer.stacked(k) for k in range(4))
+        P, A, D = int(obs.shape[1]), self.num_agents, self.obs_dim
+        T = hi - lo
+        b, d = self._bufs, self._dims
+        for name, t, shape, dtype in (("obs", obs, (n, P, A, D), torch.float32),
+                                      ("actions", actions, (n, P, A, 2), torch.float32),
+                                      ("log_probs", log_probs, (n, P * A), torch.float32),
+                                      ("values", values, (n, P, 1), torch.float32),
+                                      ("returns", buffer.returns, (n, P), _F64)):
+            if (tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device
+                    or not t.is_contiguous()):
+                raise ValueError(f"buffer {name}: need a contiguous {dtype} {shape} tensor on "
+                                 f"{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            setattr(b, name, t[lo].data_ptr())
+        for f, t in self._params:
+            g = t.grad
+            if g is None:          # zero_grad(set_to_none=True) between calls
+                g = t.grad = torch.zeros_like(t)
+            if g.dtype != torch.float32 or g.device != self.device or not g.is_contiguous() \
+                    or g.shape != t.shape:
+                raise ValueError(f"{f}.grad: need a contiguous float32 tensor like the parameter")
+            setattr(b, f, t.data_ptr())
+            setattr(b, "grad_" + f, g.data_ptr())
+        d.num_parallel, d.num_steps = P, T
+        need = int(self._lib.marlnav_ppo_work_size(ctypes.byref(d)))
+        if need < 0:
+            abi.check(need, self._lib)
+        if self._work is None or self._work.numel() < need:
+            self._work = torch.empty(need, dtype=_F64, device=self.device)
+        b.work = self._work.data_ptr()
+        loss = torch.empty((), dtype=_F64, device=self.device)
+        b.loss = loss.data_ptr()
+        return loss
+
+    def actor_loss_grad(self, buffer, lo, hi):
+        """Actor loss (0-d float64 device tensor) of steps ``lo..hi`` of
+        ``buffer``; the six actor parameters' ``.grad`` are overwritten. Two
+        launches on the current stream, no synchronisation."""
+        loss = self._bind(buffer, lo, hi)
+        abi.check(self._lib.marlnav_ppo_actor_grad(
+            ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon, self.ent_const,
+            _stream(self.device)), self._lib)
+        return loss
+
+    def critic_loss_grad(self, buffer, lo, hi):
+        """Critic loss (0-d float64 device tensor) of steps ``lo..hi``; the
+        four critic parameters' ``.grad`` are overwritten."""
+        loss = self._bind(buffer, lo, hi)
+        abi.check(self._lib.marlnav_ppo_critic_grad(
+            ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon,
+            _stream(self.device)), self._lib)
+        return loss
+
+
+def _train(loss_grad, buffer, optimizer, num_epochs, batch_size, log):
+    if buffer.returns is None:
+        raise RuntimeError("the rollout buffer has no returns yet: call "
+                           "buffer.process_rewards(gamma) (or collect()) before training")
+    bounds = minibatch_bounds(len(buffer), batch_size)
+    for _ in range(int(num_epochs)):
+        for lo, hi in bounds:
+            loss = loss_grad(buffer, lo, hi)
+            optimizer.step()
+            if log is not None:
+                log.append(loss)
+
+
+def train_actor(ppo, buffer, optimizer, num_epochs, batch_size, log=None):
+    """MAPPO.train_actor (models.py:160-178): per epoch and minibatch
+    (``minibatch_bounds``) the fused loss and gradients, ``optimizer.step()``,
+    then ``log.append(loss)`` with the loss left on the device. ``optimizer``
+    is the caller's (the reference's: ``Adam(actor.parameters(), lr,
+    maximize=True)``). Nothing is printed and nothing synchronises."""
+    _train(ppo.actor_loss_grad, buffer, optimizer, num_epochs, batch_size, log)
+
+
+def train_critic(ppo, buffer, optimizer, num_epochs, batch_size, log=None):
+    """MAPPO.train_critic (models.py:180-198), as ``train_actor``."""
+    _train(ppo.critic_loss_grad, buffer, optimizer, num_epochs, batch_size, log)
