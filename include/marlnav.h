@@ -1,7 +1,8 @@
 /*
  * marlnav.h - C ABI of the MI355X (gfx950) environment-step library
  * (libmarlnav.so, built from marl-nav_amd/csrc/marlnav_step.hip,
- * marlnav_rollout.hip, marlnav_policy.hip and marlnav_ppo.hip).
+ * marlnav_rollout.hip, marlnav_policy.hip, marlnav_ppo.hip and
+ * marlnav_adam.hip).
  *
  * The reference (JussiM01/MARL-nav) has no FFI: its boundary is the Python
  * class `Env` (marlnav/environment.py:8-286). Each entry point below replaces
@@ -315,6 +316,65 @@ int marlnav_ppo_actor_grad(const MarlnavPpoDims *dims, const MarlnavPpoBuffers *
  * four critic weights; writes the four critic gradients and loss. */
 int marlnav_ppo_critic_grad(const MarlnavPpoDims *dims, const MarlnavPpoBuffers *bufs,
                             double epsilon, void *stream);
+
+/* One Adam step over up to MARLNAV_ADAM_MAX_TENSORS parameter tensors of one
+ * network: torch.optim.Adam (models.py:71-74) with weight_decay = 0 and
+ * amsgrad = False. */
+#define MARLNAV_ADAM_MAX_TENSORS 8
+
+typedef struct MarlnavAdamDims {
+    int32_t num_tensors;     /* used slots, 1..MARLNAV_ADAM_MAX_TENSORS       */
+    int32_t maximize;        /* 0: descend, 1: ascend (the actor's optimiser) */
+    int64_t numel[MARLNAV_ADAM_MAX_TENSORS]; /* elements per used slot, >= 1  */
+    double lr, beta1, beta2, eps; /* lr >= 0, betas in [0, 1), eps >= 0       */
+    int64_t reserved;        /* must be 0                                     */
+} MarlnavAdamDims;
+
+/* Device pointers of one Adam step, fp32, contiguous, numel[i] elements each;
+ * any 4-byte alignment (a slot whose four pointers are all 16-byte aligned
+ * takes the vector path). The slots must not overlap. */
+typedef struct MarlnavAdamBuffers {
+    float *param[MARLNAV_ADAM_MAX_TENSORS];       /* updated in place         */
+    const float *grad[MARLNAV_ADAM_MAX_TENSORS];
+    float *exp_avg[MARLNAV_ADAM_MAX_TENSORS];     /* first moment, in place   */
+    float *exp_avg_sq[MARLNAV_ADAM_MAX_TENSORS];  /* second moment, in place  */
+    /* marlnav_adam_state_size() bytes, 8-byte aligned: the int64 step count
+     * (the first 8 bytes; all zero = no step taken yet) and the step's
+     * scalars derived from it. Owned by the library between calls. */
+    void *state;
+} MarlnavAdamBuffers;
+
+/* Bytes of MarlnavAdamBuffers.state. */
+int64_t marlnav_adam_state_size(void);
+
+/* One optimiser step. With k the count in `state` after this call's
+ * increment and g = maximize ? -grad : grad:
+ *   m = beta1 m + (1 - beta1) g         v = beta2 v + (1 - beta2) g^2
+ *   p -= lr / (1 - beta1^k) * m / (sqrt(v) / sqrt(1 - beta2^k) + eps)
+ * The bias corrections are evaluated in fp64 from the device count; every
+ * element is updated in fp64 and m, v, p are rounded to fp32 once on the
+ * store. Two launches on `stream`: one thread advances the count and
+ * publishes the step's scalars, then thread = 4 elements over all slots. No
+ * synchronisation, no host copy of the count (a captured graph replays
+ * correctly), no atomics: equal inputs give equal bits. lr, the betas, eps
+ * and maximize travel as launch arguments: a captured graph keeps the values
+ * of capture time. */
+int marlnav_adam_step(const MarlnavAdamDims *dims, const MarlnavAdamBuffers *bufs,
+                      void *stream);
+
+/* One minibatch update in one call: what marlnav_ppo_actor_grad /
+ * marlnav_ppo_critic_grad enqueue, then marlnav_adam_step over that network's
+ * tensors, all on `stream`. The Adam table must be that network's: param[i],
+ * grad[i] and numel[i] equal the weights, the grad_ pointers and the sizes of
+ * `bufs` in declaration order (six slots for the actor, four for the critic);
+ * anything else is MARLNAV_EINVAL before any launch. */
+int marlnav_ppo_actor_update(const MarlnavPpoDims *dims, const MarlnavPpoBuffers *bufs,
+                             double epsilon, double ent_const,
+                             const MarlnavAdamDims *adam_dims,
+                             const MarlnavAdamBuffers *adam_bufs, void *stream);
+int marlnav_ppo_critic_update(const MarlnavPpoDims *dims, const MarlnavPpoBuffers *bufs,
+                              double epsilon, const MarlnavAdamDims *adam_dims,
+                              const MarlnavAdamBuffers *adam_bufs, void *stream);
 
 /* Testing hook (not part of the reference's interface): restrict the step /
  * observe kernel selection to one family, process-wide. 0 = automatic (the

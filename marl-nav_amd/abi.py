@@ -107,10 +107,30 @@ class MarlnavPpoBuffers(ctypes.Structure):
     _fields_ = [(n, _P) for n in PPO_BUFFER_FIELDS]
 
 
+ADAM_MAX_TENSORS = 8
+ADAM_POINTER_FIELDS = ("param", "grad", "exp_avg", "exp_avg_sq")
+
+
+class MarlnavAdamDims(ctypes.Structure):
+    _fields_ = [("num_tensors", ctypes.c_int32),
+                ("maximize", ctypes.c_int32),
+                ("numel", ctypes.c_int64 * ADAM_MAX_TENSORS),
+                ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("reserved", ctypes.c_int64)]
+
+
+class MarlnavAdamBuffers(ctypes.Structure):
+    _fields_ = ([(n, _P * ADAM_MAX_TENSORS) for n in ADAM_POINTER_FIELDS]
+                + [("state", _P)])
+
+
 EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_formation_obs",
            "marlnav_counter_slots", "marlnav_counters_total",
            "marlnav_returns_work_size", "marlnav_discounted_returns", "marlnav_policy_act",
            "marlnav_ppo_work_size", "marlnav_ppo_actor_grad", "marlnav_ppo_critic_grad",
+           "marlnav_adam_state_size", "marlnav_adam_step",
+           "marlnav_ppo_actor_update", "marlnav_ppo_critic_update",
            "marlnav_last_error", "marlnav_abi_version",
            "marlnav_debug_force_family", "marlnav_debug_last_family",
            "marlnav_debug_acos_range", "marlnav_debug_fastdiv_check")
@@ -151,6 +171,17 @@ def _declare(lib):
     lib.marlnav_ppo_actor_grad.restype = c.c_int
     lib.marlnav_ppo_critic_grad.argtypes = [ppo_dims_p, ppo_bufs_p, c.c_double, _P]
     lib.marlnav_ppo_critic_grad.restype = c.c_int
+    adam_dims_p, adam_bufs_p = c.POINTER(MarlnavAdamDims), c.POINTER(MarlnavAdamBuffers)
+    lib.marlnav_adam_state_size.argtypes = []
+    lib.marlnav_adam_state_size.restype = c.c_int64
+    lib.marlnav_adam_step.argtypes = [adam_dims_p, adam_bufs_p, _P]
+    lib.marlnav_adam_step.restype = c.c_int
+    lib.marlnav_ppo_actor_update.argtypes = [ppo_dims_p, ppo_bufs_p, c.c_double, c.c_double,
+                                             adam_dims_p, adam_bufs_p, _P]
+    lib.marlnav_ppo_actor_update.restype = c.c_int
+    lib.marlnav_ppo_critic_update.argtypes = [ppo_dims_p, ppo_bufs_p, c.c_double,
+                                              adam_dims_p, adam_bufs_p, _P]
+    lib.marlnav_ppo_critic_update.restype = c.c_int
     lib.marlnav_last_error.argtypes = []
     lib.marlnav_last_error.restype = c.c_char_p
     lib.marlnav_abi_version.argtypes = []

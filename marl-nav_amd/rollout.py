@@ -25,6 +25,13 @@ as one HIP scan instead of a Python loop of T x 3 small tensor ops.
   ``marlnav_ppo_actor_grad`` / ``marlnav_ppo_critic_grad``), and
   ``train_actor`` / ``train_critic`` / ``minibatch_bounds``, the loops of
   models.py:160-198 around them and the caller's ``torch.optim`` optimiser.
+* ``FusedAdam(params, lr, betas, eps, maximize)`` - ``torch.optim.Adam`` as
+  the reference constructs it (models.py:71-74) in one launch over all of a
+  network's parameters with the step count on the device (libmarlnav.so
+  ``marlnav_adam_step``). Given one, ``train_actor`` / ``train_critic`` issue a
+  whole minibatch update (loss, gradients, Adam) as one C call
+  (``FusedPPO.actor_update`` / ``critic_update``), and an epoch of them can be
+  captured in a graph and replayed.
 
 Numerics: float64 like the reference (its accumulator is
 ``torch.zeros(P, dtype=float)``); the returns recursion is evaluated in the
@@ -450,16 +457,240 @@ class FusedPPO(object):
             _stream(self.device)), self._lib)
         return loss
 
+    def _network_params(self, which):
+        """The parameter tensors of 'actor' / 'critic' in ``_POLICY_PARAMS``
+        order."""
+        return [t for f, t in self._params if f.startswith(which)]
 
-def _train(loss_grad, buffer, optimizer, num_epochs, batch_size, log):
+    def actor_update(self, buffer, lo, hi, adam):
+        """``actor_loss_grad(buffer, lo, hi)`` then ``adam.step()`` as ONE C
+        call (``marlnav_ppo_actor_update``): four launches on the current
+        stream with no host work between them, bit-identical to the two
+        calls. ``adam``: a ``FusedAdam`` over exactly the six actor
+        parameters in ``_POLICY_PARAMS`` order (the library refuses any other
+        table). Returns the loss (0-d float64 device tensor)."""
+        loss = self._bind(buffer, lo, hi)
+        ad, ab = adam._bind()
+        abi.check(self._lib.marlnav_ppo_actor_update(
+            ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon, self.ent_const,
+            ctypes.byref(ad), ctypes.byref(ab), _stream(self.device)), self._lib)
+        return loss
+
+    def critic_update(self, buffer, lo, hi, adam):
+        """``critic_loss_grad`` then ``adam.step()`` as one C call
+        (``marlnav_ppo_critic_update``); ``adam`` over the four critic
+        parameters. As ``actor_update``."""
+        loss = self._bind(buffer, lo, hi)
+        ad, ab = adam._bind()
+        abi.check(self._lib.marlnav_ppo_critic_update(
+            ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon,
+            ctypes.byref(ad), ctypes.byref(ab), _stream(self.device)), self._lib)
+        return loss
+
+
+class FusedAdam(object):
+    """``torch.optim.Adam`` with ``weight_decay=0`` and ``amsgrad=False`` (how
+    the reference constructs it, models.py:71-74) over up to 8 contiguous fp32
+    parameters on one HIP device, as one call of libmarlnav.so
+    ``marlnav_adam_step``: one launch advances the step count, which lives on
+    the device, the next updates every element of every parameter. Nothing
+    synchronises and the host keeps no count, so steps can be captured in a
+    graph and replayed.
+
+    ``exp_avg`` and ``exp_avg_sq`` of all parameters are views of one flat
+    fp32 allocation (each segment padded to 16 bytes), created zeroed here and
+    never reallocated: ``load_state_dict`` copies into them in place, so the
+    pointers a captured graph holds stay valid. ``.grad`` is allocated
+    (zeros) where it is None.
+
+    ``param_groups`` is a one-entry list of dicts as ``torch.optim`` keeps it;
+    ``lr``, ``betas``, ``eps`` and ``maximize`` are read from it at every call
+    and travel as launch arguments, so a captured graph keeps the values of
+    capture time (change them, then capture again).
+
+    ``state_dict()`` / ``load_state_dict()`` speak ``torch.optim.Adam``'s
+    format, so a checkpoint moves between the two in either direction."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, maximize=False,
+                 weight_decay=0, amsgrad=False):
+        if weight_decay != 0:
+            raise ValueError(f"FusedAdam: weight_decay={weight_decay} is unsupported "
+                             "(the reference's Adam has none)")
+        if amsgrad:
+            raise ValueError("FusedAdam: amsgrad=True is unsupported")
+        params = list(params)
+        if not 1 <= len(params) <= abi.ADAM_MAX_TENSORS:
+            raise ValueError(f"FusedAdam takes 1..{abi.ADAM_MAX_TENSORS} parameter tensors, "
+                             f"got {len(params)}")
+        dev = params[0].device
+        if dev.type != "cuda":
+            raise RuntimeError("FusedAdam runs on a HIP device (no CPU fallback); "
+                               f"the parameters are on {dev}")
+        for i, p in enumerate(params):
+            if p.dtype != torch.float32 or p.device != dev or not p.is_contiguous() \
+                    or p.numel() < 1:
+                raise ValueError(f"params[{i}]: need a non-empty contiguous float32 tensor on "
+                                 f"{dev}, got {p.dtype} {tuple(p.shape)} on {p.device}, "
+                                 f"contiguous={p.is_contiguous()}")
+        self.device = dev
+        self.param_groups = [{"params": params, "lr": lr, "betas": tuple(betas), "eps": eps,
+                              "maximize": bool(maximize), "weight_decay": 0, "amsgrad": False}]
+        self._hyper()                       # refuses bad values now rather than at step()
+        self._lib = abi.load_library()
+        offs, at = [], 0
+        for p in params:
+            offs.append(at)
+            at += (p.numel() + 3) // 4 * 4  # segments start on 16 bytes
+        self._flat = torch.zeros(2 * at, dtype=torch.float32, device=dev)
+        self.exp_avg = [self._flat[o:o + p.numel()].view(p.shape) for o, p in zip(offs, params)]
+        self.exp_avg_sq = [self._flat[at + o:at + o + p.numel()].view(p.shape)
+                           for o, p in zip(offs, params)]
+        nstate = int(self._lib.marlnav_adam_state_size())
+        self._state = torch.zeros((nstate + 7) // 8, dtype=torch.int64, device=dev)
+        self._dims = abi.MarlnavAdamDims(num_tensors=len(params))
+        self._bufs = abi.MarlnavAdamBuffers(state=self._state.data_ptr())
+        for i, p in enumerate(params):
+            self._dims.numel[i] = p.numel()
+            self._bufs.exp_avg[i] = self.exp_avg[i].data_ptr()
+            self._bufs.exp_avg_sq[i] = self.exp_avg_sq[i].data_ptr()
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+
+    @property
+    def params(self):
+        return self.param_groups[0]["params"]
+
+    def _hyper(self):
+        g = self.param_groups[0]
+        if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False):
+            raise ValueError("FusedAdam: weight_decay and amsgrad are unsupported")
+        lr, (b1, b2), eps = float(g["lr"]), g["betas"], float(g["eps"])
+        if not 0.0 <= lr < float("inf"):
+            raise ValueError(f"FusedAdam: lr={lr} must be finite and >= 0")
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"FusedAdam: betas={g['betas']} outside [0, 1)")
+        if not 0.0 <= eps < float("inf"):
+            raise ValueError(f"FusedAdam: eps={eps} must be finite and >= 0")
+        return lr, float(b1), float(b2), eps, 1 if g["maximize"] else 0
+
+    def _bind(self):
+        """The call's structs from the live tensors and ``param_groups``."""
+        d, b = self._dims, self._bufs
+        d.lr, d.beta1, d.beta2, d.eps, d.maximize = self._hyper()
+        for i, p in enumerate(self.params):
+            g = p.grad
+            if g is None:
+                raise RuntimeError(f"FusedAdam: params[{i}].grad is None (zero_grad("
+                                   "set_to_none=True) with no gradient written since)")
+            if g.dtype != torch.float32 or g.device != self.device or not g.is_contiguous() \
+                    or g.shape != p.shape:
+                raise ValueError(f"params[{i}].grad: need a contiguous float32 tensor like the "
+                                 "parameter")
+            b.param[i] = p.data_ptr()
+            b.grad[i] = g.data_ptr()
+        return d, b
+
+    def step(self):
+        """One Adam step of every parameter from its ``.grad``: one
+        ``marlnav_adam_step`` (two launches) on the current stream."""
+        d, b = self._bind()
+        abi.check(self._lib.marlnav_adam_step(ctypes.byref(d), ctypes.byref(b),
+                                              _stream(self.device)), self._lib)
+
+    def zero_grad(self, set_to_none=False):
+        """Zero the gradients in place (the default here, unlike torch's: the
+        fused gradient kernels overwrite ``.grad``, and a graph keeps its
+        pointer); ``set_to_none=True`` drops them instead."""
+        for p in self.params:
+            if set_to_none:
+                p.grad = None
+            elif p.grad is not None:
+                p.grad.zero_()
+
+    def covers(self, tensors):
+        """True when the parameters are exactly ``tensors``, in that order."""
+        mine = self.params
+        return len(mine) == len(tensors) and all(a is b for a, b in zip(mine, tensors))
+
+    def step_count(self):
+        """The device's step count (synchronises)."""
+        return int(self._state[0].item())
+
+    def state_dict(self):
+        """``torch.optim.Adam``'s format: ``state[i]`` = ``step`` (0-d float32,
+        on the CPU as Adam keeps it), ``exp_avg``, ``exp_avg_sq`` (copies);
+        ``param_groups`` with Adam's keys. ``torch.optim.Adam`` over the same
+        parameters loads it. Synchronises."""
+        k = self.step_count()
+        state = {i: {"step": torch.tensor(float(k), dtype=torch.float32),
+                     "exp_avg": self.exp_avg[i].clone(), "exp_avg_sq": self.exp_avg_sq[i].clone()}
+                 for i in range(len(self.params))} if k else {}
+        g = self.param_groups[0]
+        group = {"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"], "weight_decay": 0,
+                 "amsgrad": False, "maximize": bool(g["maximize"]), "foreach": None,
+                 "capturable": False, "differentiable": False, "fused": None,
+                 "decoupled_weight_decay": False, "params": list(range(len(self.params)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, state_dict):
+        """Load a ``state_dict()`` of this class or of a ``torch.optim.Adam``
+        over the same parameters: one group, no weight decay, no amsgrad, one
+        ``step`` for all parameters (anything else is a ValueError). Moments
+        and count are copied IN PLACE into the existing storage; ``lr``,
+        ``betas``, ``eps`` and ``maximize`` are taken from the group."""
+        groups, state = state_dict["param_groups"], state_dict["state"]
+        n = len(self.params)
+        if len(groups) != 1 or len(groups[0]["params"]) != n:
+            raise ValueError(f"FusedAdam: need one parameter group of {n} parameters")
+        g = groups[0]
+        if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False):
+            raise ValueError("FusedAdam: a state with weight_decay or amsgrad is unsupported")
+        ids = list(g["params"])
+        have = [i for i in ids if i in state and len(state[i])]
+        if have and len(have) != n:
+            raise ValueError("FusedAdam: the state covers some parameters only; their step "
+                             "counts differ")
+        steps = [float(state[i]["step"]) for i in have]
+        if any(s != steps[0] for s in steps):
+            raise ValueError(f"FusedAdam: the parameters' step counts differ ({steps}); one "
+                             "count serves all")
+        k = steps[0] if steps else 0.0
+        if k < 0 or k != int(k):
+            raise ValueError(f"FusedAdam: step={k} is not a whole number >= 0")
+        for j, i in enumerate(have):
+            for name, dst in (("exp_avg", self.exp_avg[j]), ("exp_avg_sq", self.exp_avg_sq[j])):
+                src = state[i][name]
+                if tuple(src.shape) != tuple(dst.shape):
+                    raise ValueError(f"FusedAdam: state[{i}].{name} has shape "
+                                     f"{tuple(src.shape)}, the parameter {tuple(dst.shape)}")
+        for j, i in enumerate(have):
+            self.exp_avg[j].copy_(state[i]["exp_avg"])
+            self.exp_avg_sq[j].copy_(state[i]["exp_avg_sq"])
+        if not have:
+            self._flat.zero_()
+        self._state.zero_()
+        self._state[0] = int(k)
+        mine = self.param_groups[0]
+        mine.update(lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"],
+                    maximize=bool(g.get("maximize", False)))
+        self._hyper()
+
+
+def _train(loss_grad, update, network, buffer, optimizer, num_epochs, batch_size, log):
     if buffer.returns is None:
         raise RuntimeError("the rollout buffer has no returns yet: call "
                            "buffer.process_rewards(gamma) (or collect()) before training")
     bounds = minibatch_bounds(len(buffer), batch_size)
+    # a FusedAdam over exactly this network's parameters: one C call per
+    # minibatch; any other optimiser: the two calls
+    one_call = isinstance(optimizer, FusedAdam) and optimizer.covers(network)
     for _ in range(int(num_epochs)):
         for lo, hi in bounds:
-            loss = loss_grad(buffer, lo, hi)
-            optimizer.step()
+            if one_call:
+                loss = update(buffer, lo, hi, optimizer)
+            else:
+                loss = loss_grad(buffer, lo, hi)
+                optimizer.step()
             if log is not None:
                 log.append(loss)
 
@@ -469,10 +700,18 @@ def train_actor(ppo, buffer, optimizer, num_epochs, batch_size, log=None):
     (``minibatch_bounds``) the fused loss and gradients, ``optimizer.step()``,
     then ``log.append(loss)`` with the loss left on the device. ``optimizer``
     is the caller's (the reference's: ``Adam(actor.parameters(), lr,
-    maximize=True)``). Nothing is printed and nothing synchronises."""
-    _train(ppo.actor_loss_grad, buffer, optimizer, num_epochs, batch_size, log)
+    maximize=True)``). Nothing is printed and nothing synchronises.
+
+    With a ``FusedAdam`` over exactly the actor's six parameters in
+    ``_POLICY_PARAMS`` order (``FusedAdam(actor.parameters(), ...)`` of the
+    reference's module) the two calls of a minibatch become the one call
+    ``ppo.actor_update``, with equal bits, and a whole epoch can be captured
+    in a graph."""
+    _train(ppo.actor_loss_grad, ppo.actor_update, ppo._network_params("actor"), buffer,
+           optimizer, num_epochs, batch_size, log)
 
 
 def train_critic(ppo, buffer, optimizer, num_epochs, batch_size, log=None):
     """MAPPO.train_critic (models.py:180-198), as ``train_actor``."""
-    _train(ppo.critic_loss_grad, buffer, optimizer, num_epochs, batch_size, log)
+    _train(ppo.critic_loss_grad, ppo.critic_update, ppo._network_params("critic"), buffer,
+           optimizer, num_epochs, batch_size, log)

@@ -1,6 +1,10 @@
 """Time of one PPO minibatch update (loss, gradients, optimiser step) of the
-actor and of the critic on one GPU, three arms:
+actor and of the critic on one GPU, four arms:
 
+* ``onecall``: ``FusedPPO.actor_update`` / ``critic_update`` with a
+  ``FusedAdam``: loss, gradients and the Adam step as one C call
+  (libmarlnav.so ``marlnav_ppo_actor_update`` / ``marlnav_ppo_critic_update``),
+  no host work between its launches;
 * ``fused``: ``FusedPPO.actor_loss_grad`` / ``critic_loss_grad`` (two launches
   each, libmarlnav.so ``marlnav_ppo_actor_grad`` / ``marlnav_ppo_critic_grad``)
   on the RolloutBuffer's stacked storage, then ``optimizer.step()``;
@@ -20,7 +24,12 @@ alternating ``--reps`` times; medians per update.
 Also each fused call alone (a hipGraph of ``--chain`` calls replayed under
 events, so the host's enqueue rate is not what is measured) next to its byte
 and FMA counts: bytes are the minibatch read once plus the workspace written
-and read back; the byte bound is at 6.3 TB/s achievable HBM.
+and read back; the byte bound is at 6.3 TB/s achievable HBM. The Adam call
+alone likewise (``FusedAdam.step``; bytes: param, grad and the two moments
+read, param and the moments written back, seven fp32 streams of numel), and
+one epoch of ``train_actor`` + ``train_critic`` with ``FusedAdam`` (the
+minibatches of ``minibatch_bounds(steps, --epoch-batch)``) captured in a graph
+and replayed, against the same epoch issued eagerly.
 
     python scripts/ppo_bench.py [--shapes 65536x3x3,16384x3x3,1024x3x8,4096x16x32]
 """
@@ -86,7 +95,7 @@ def timed(fn, iters):
     return a.elapsed_time(b) * 1e3 / iters   # us
 
 
-def graph_time(fn, chain, replays):
+def graph_time(fn, chain, replays, iters=1):
     for _ in range(3):
         fn()
     torch.cuda.synchronize()
@@ -95,7 +104,7 @@ def graph_time(fn, chain, replays):
         for _ in range(chain):
             fn()
     g.replay()
-    ts = sorted(timed(g.replay, 1) / chain for _ in range(replays))
+    ts = sorted(timed(g.replay, iters) / chain for _ in range(replays))
     return ts[len(ts) // 2]
 
 
@@ -132,6 +141,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--chain", type=int, default=20)
     ap.add_argument("--mvn-envs", type=int, default=1024)
+    ap.add_argument("--epoch-batch", type=int, default=2,
+                    help="steps per minibatch of the captured epoch")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("ppo_bench.py needs a HIP device")
@@ -167,6 +178,9 @@ def main():
         ppo = pkg.FusedPPO(actor, critic, EPSILON, ENT_CONST)
         opt_a = torch.optim.Adam(actor.parameters(), lr=LR, maximize=True)
         opt_c = torch.optim.Adam(critic.parameters(), lr=LR, maximize=False)
+        # the one-call arm's optimisers: their own moments over the same parameters
+        adam_a = pkg.FusedAdam(actor.parameters(), lr=LR, maximize=True)
+        adam_c = pkg.FusedAdam(critic.parameters(), lr=LR, maximize=False)
         names = {"actor": (actor, ("fc1", "fc_mu", "fc_std")), "critic": (critic, ("fc1", "fc2"))}
 
         def weights(which):
@@ -184,6 +198,12 @@ def main():
         def fused_critic():
             ppo.critic_loss_grad(buf, 0, T)
             opt_c.step()
+
+        def onecall_actor():
+            ppo.actor_update(buf, 0, T, adam_a)
+
+        def onecall_critic():
+            ppo.critic_update(buf, 0, T, adam_c)
 
         def torch_actor():
             opt_a.zero_grad()
@@ -218,8 +238,8 @@ def main():
             pp.critic_loss(weights("critic"), obs, vals, rets, EPSILON).backward()
             opt_c.step()
 
-        arms = {"fused": (fused_actor, fused_critic), "torch": (torch_actor, torch_critic),
-                "mvn": (mvn_actor, mvn_critic)}
+        arms = {"onecall": (onecall_actor, onecall_critic), "fused": (fused_actor, fused_critic),
+                "torch": (torch_actor, torch_critic), "mvn": (mvn_actor, mvn_critic)}
         for fa, fc in arms.values():
             for _ in range(2):
                 fa()
@@ -235,6 +255,8 @@ def main():
                 assert bool(torch.isfinite(p).all())
                 assert not torch.equal(p, start[id(p)])
 
+        assert adam_a.step_count() == adam_c.step_count() == 2 + a.reps * a.iters
+
         k_actor = graph_time(lambda: ppo.actor_loss_grad(buf, 0, T), a.chain, 7)
         k_critic = graph_time(lambda: ppo.critic_loss_grad(buf, 0, T), a.chain, 7)
         a_blocks = actor_blocks(M)
@@ -245,12 +267,39 @@ def main():
         c_bytes = 4 * N * AD + 12 * N + 2 * 8 * chunks * (H * AD + 2 * H + 2) \
             + 2 * 4 * (H * AD + 2 * H + 1) + (2 * 4 * N * cdiv(H, 64) * 64 if split else 0)
         c_fma32, c_fma64 = N * (H * AD + H) * fwd, N * H * AD
+        # the Adam call alone, and one epoch eager against its graph
+        k_adam_a = graph_time(adam_a.step, a.chain, 7)
+        k_adam_c = graph_time(adam_c.step, a.chain, 7)
+        n_a = sum(p.numel() for p in actor.parameters())
+        n_c = sum(p.numel() for p in critic.parameters())
+        bounds = pkg.minibatch_bounds(T, a.epoch_batch)
+
+        def epoch():
+            pkg.train_actor(ppo, buf, adam_a, 1, a.epoch_batch)
+            pkg.train_critic(ppo, buf, adam_c, 1, a.epoch_batch)
+
+        epoch()
+        eager = sorted(timed(epoch, a.iters) for _ in range(a.reps))[a.reps // 2]
+        count = adam_a.step_count()
+        replayed = graph_time(epoch, 1, a.reps, iters=a.iters)
+        # 3 warm-up epochs, then 1 + reps * iters replays: the count followed them
+        assert adam_a.step_count() == count + (4 + a.reps * a.iters) * len(bounds)
         rec = {"shape": shape, "hidden": H, "steps": T, "agent_rows": M, "env_rows": N,
                "actor_us": {k: round(v[0], 1) for k, v in med.items()},
                "critic_us": {k: round(v[1], 1) for k, v in med.items()},
                "mvn_envs": Pm,
+               "actor_onecall_vs_fused": round(med["fused"][0] / med["onecall"][0], 2),
+               "critic_onecall_vs_fused": round(med["fused"][1] / med["onecall"][1], 2),
                "actor_speedup_vs_torch": round(med["torch"][0] / med["fused"][0], 2),
                "critic_speedup_vs_torch": round(med["torch"][1] / med["fused"][1], 2),
+               "adam_actor_call_us": round(k_adam_a, 1), "adam_actor_bytes": 28 * n_a,
+               "adam_critic_call_us": round(k_adam_c, 1), "adam_critic_bytes": 28 * n_c,
+               "adam_actor_share_of_byte_bound":
+                   round(28 * n_a / PEAK_BYTES_PER_S * 1e6 / k_adam_a, 5),
+               "adam_critic_share_of_byte_bound":
+                   round(28 * n_c / PEAK_BYTES_PER_S * 1e6 / k_adam_c, 5),
+               "epoch_minibatches": len(bounds), "epoch_eager_us": round(eager, 1),
+               "epoch_graph_us": round(replayed, 1),
                "reps": {k: [[round(x, 1) for x in v] for v in ts] for k, ts in times.items()},
                "actor_call_us": round(k_actor, 1), "actor_bytes": a_bytes,
                "actor_fma_fp64": a_fma64, "actor_blocks": a_blocks,
