@@ -249,6 +249,70 @@ typedef struct MarlnavPolicyBuffers {
 int marlnav_policy_act(const MarlnavPolicyDims *dims, const MarlnavPolicyBuffers *bufs,
                        uint64_t policy_seed, uint64_t step_idx, void *stream);
 
+/* Device pointers of one rollout of T steps of P envs: the stacked storage of
+ * the six entries MAPPO.get_data keeps per step (models.py:120), row t of each
+ * being step t, plus what the call needs beside them. Contiguous; fp32 unless
+ * noted. Rows may start at any offset the entry's own type allows (a row of
+ * `actions` is always 8-byte aligned, as marlnav_step needs; where a row of
+ * `actions` is not 16-byte aligned that step runs the generic wave kernel,
+ * and where a row of `obs` is not, that policy launch loads narrower: both
+ * bit-identical to the aligned paths). */
+typedef struct MarlnavRolloutBuffers {
+    float *obs;                /* (T, P, A, D) normalised observations the policy
+                                  read at step t (models.py:110, :113, :124)     */
+    float *actions;            /* (T, P, A, 2) policy-scale actions (models.py:114) */
+    float *log_probs;          /* (T, P*A)     (models.py:115)                   */
+    float *values;             /* (T, P)       (models.py:120)                   */
+    float *rewards;            /* (T, P)       (models.py:116)                   */
+    uint8_t *done;             /* (T, P) bool: terminated | truncated (models.py:117);
+                                  holds `terminated` until the merge at the end  */
+    uint8_t *truncated;        /* (T, P) scratch: the steps' `truncated` flags   */
+    /* optional standard normals of dist.sample() (models.py:114), row t for
+     * step t; NULL: drawn by the policy kernel at policy_step_idx0 + t */
+    const float *eps;          /* (T, P*A, 2)                                    */
+    /* optional MAPPO._process_rewards (models.py:131-148) over rewards and done
+     * with `gamma`, as marlnav_discounted_returns: all three given or all NULL */
+    double *returns;           /* (T, P) fp64 out                                */
+    double *returns_stats;     /* 2 fp64 out (mean, std)                         */
+    double *returns_work;      /* marlnav_returns_work_size(P) fp64 scratch      */
+} MarlnavRolloutBuffers;
+
+/* MAPPO.get_data (models.py:106-125) for T steps of one env shard and, with
+ * the returns pointers, _process_rewards (:131-148), enqueued on `stream` by
+ * one call with no host work between the launches:
+ *   marlnav_observe of the current state into env->obs, and its normalised
+ *     form (obs - norm_mean[k]) / norm_scale[k] (one IEEE subtraction and one
+ *     IEEE division, as the step kernels' fused ObsNormalizer) into obs row 0
+ *     (models.py:110);
+ *   for t = 0 .. T-1 what marlnav_policy_act enqueues on obs row t, writing
+ *     actions / log_probs / values row t (eps row t, or the kernel's stream at
+ *     policy_step_idx0 + t), then what marlnav_step enqueues at step index
+ *     env_step_idx0 + t with actions row t, reward = rewards row t,
+ *     terminated = done row t, truncated = truncated row t and obs_norm =
+ *     obs row t + 1, the last step's being env->obs_norm (models.py:113-124);
+ *   done[i] = (done[i] | truncated[i]) != 0 over the T*P flags (models.py:117);
+ *   what marlnav_discounted_returns enqueues, when asked for.
+ * env: the table of a marlnav_step call with native re-init (fresh_states
+ *   NULL) and both MARLNAV_WRITE_OBS_NORM and MARLNAV_SCALE_ACTIONS set in
+ *   params->flags; its actions, reward, terminated and truncated fields are
+ *   ignored, obs (raw observations, overwritten every step) and obs_norm (the
+ *   observations after the last step; must not overlap rollout->obs) are used.
+ *   With states_out given the two state buffers swap roles every step, so the
+ *   current states are in `states` after an even T and in `states_out` after
+ *   an odd one; without it every step runs in place.
+ * policy: the weights are read live at every step; obs_norm, eps, actions,
+ *   log_probs, values and eps_out are ignored. pdims must describe the same
+ *   shard: num_parallel, num_agents and env_offset of dims, obs_dim = D.
+ * Everything is validated before the first launch (MARLNAV_EINVAL, the
+ * message names the field). A failing launch ends the call at once with its
+ * code; the message names the step, and nothing further is enqueued. */
+int marlnav_rollout_collect(const MarlnavDims *dims, const MarlnavParams *params,
+                            const MarlnavStepBuffers *env, uint64_t env_step_idx0,
+                            const MarlnavPolicyDims *pdims, const MarlnavPolicyBuffers *policy,
+                            uint64_t policy_seed, uint64_t policy_step_idx0,
+                            const MarlnavRolloutBuffers *rollout, int64_t T, double gamma,
+                            void *stream);
+
 /* Shapes of one PPO minibatch: rows lo..hi of a stacked rollout, T = hi - lo
  * steps of P envs. N = T*P env rows, M = N*A agent rows in (t, p, a) order. */
 typedef struct MarlnavPpoDims {

@@ -8,8 +8,8 @@ The package directory is ``marl-nav_amd/``; import it as ``marlnav_amd``
 """
 from . import abi, rollout, shard
 from .environment import Env
-from .rollout import (FusedAdam, FusedPolicy, FusedPPO, RolloutBuffer, collect, minibatch_bounds, train_actor,
-                      train_critic)
+from .rollout import (FusedAdam, FusedPolicy, FusedPPO, RolloutBuffer, collect, collect_fused,
+                      minibatch_bounds, train_actor, train_critic)
 from .utils import (ActionScaler, ConstantSampler, MockInitializer, MockSampler,
                     ObsNormalizer, Observations, TriangleIntitializer, action_sampler, default_args,
                     init_sampler, set_all_seeds, set_env_params, set_init_params,
@@ -20,4 +20,4 @@ __all__ = ["Env", "Observations", "ObsNormalizer", "ActionScaler", "MockInitiali
            "action_sampler", "set_all_seeds", "set_env_params", "set_init_params",
            "set_sampler_params", "set_normalizer_params", "set_scaler_params", "default_args",
            "abi", "rollout", "shard", "FusedPolicy", "RolloutBuffer", "collect",
-           "FusedPPO", "FusedAdam", "minibatch_bounds", "train_actor", "train_critic"]
+           "collect_fused", "FusedPPO", "FusedAdam", "minibatch_bounds", "train_actor", "train_critic"]

@@ -82,6 +82,19 @@ class MarlnavPolicyBuffers(ctypes.Structure):
     _fields_ = [(n, _P) for n in POLICY_BUFFER_FIELDS]
 
 
+ROLLOUT_BUFFER_FIELDS = ("obs", "actions", "log_probs", "values", "rewards", "done", "truncated",
+                         "eps", "returns", "returns_stats", "returns_work")
+# eps is optional; the three returns pointers are given together or not at all
+ROLLOUT_REQUIRED_FIELDS = ROLLOUT_BUFFER_FIELDS[:7]
+# what marlnav_rollout_collect needs of the env's MarlnavStepBuffers
+ROLLOUT_ENV_REQUIRED = ("states", "obstacles", "target", "step_num", "terminates", "formation",
+                        "obs", "obs_norm", "norm_mean", "norm_scale")
+
+
+class MarlnavRolloutBuffers(ctypes.Structure):
+    _fields_ = [(n, _P) for n in ROLLOUT_BUFFER_FIELDS]
+
+
 class MarlnavPpoDims(ctypes.Structure):
     _fields_ = [("num_parallel", ctypes.c_int64),
                 ("num_steps", ctypes.c_int64),
@@ -128,7 +141,7 @@ class MarlnavAdamBuffers(ctypes.Structure):
 EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_formation_obs",
            "marlnav_counter_slots", "marlnav_counters_total",
            "marlnav_returns_work_size", "marlnav_discounted_returns", "marlnav_policy_act",
-           "marlnav_ppo_work_size", "marlnav_ppo_actor_grad", "marlnav_ppo_critic_grad",
+           "marlnav_rollout_collect", "marlnav_ppo_work_size", "marlnav_ppo_actor_grad", "marlnav_ppo_critic_grad",
            "marlnav_adam_state_size", "marlnav_adam_step",
            "marlnav_ppo_actor_update", "marlnav_ppo_critic_update",
            "marlnav_last_error", "marlnav_abi_version",
@@ -164,6 +177,12 @@ def _declare(lib):
     lib.marlnav_policy_act.argtypes = [c.POINTER(MarlnavPolicyDims),
                                        c.POINTER(MarlnavPolicyBuffers), c.c_uint64, c.c_uint64, _P]
     lib.marlnav_policy_act.restype = c.c_int
+    lib.marlnav_rollout_collect.argtypes = [dims_p, par_p, c.POINTER(MarlnavStepBuffers), c.c_uint64,
+                                            c.POINTER(MarlnavPolicyDims),
+                                            c.POINTER(MarlnavPolicyBuffers), c.c_uint64, c.c_uint64,
+                                            c.POINTER(MarlnavRolloutBuffers), c.c_int64, c.c_double,
+                                            _P]
+    lib.marlnav_rollout_collect.restype = c.c_int
     ppo_dims_p, ppo_bufs_p = c.POINTER(MarlnavPpoDims), c.POINTER(MarlnavPpoBuffers)
     lib.marlnav_ppo_work_size.argtypes = [ppo_dims_p]
     lib.marlnav_ppo_work_size.restype = c.c_int64

@@ -43,6 +43,10 @@ constexpr int kPoolMax = 4;
 using StepFn = int (*)(const MarlnavDims *, const MarlnavParams *, const MarlnavStepBuffers *,
                        uint64_t, void *);
 using ErrFn = const char *(*)(void);
+using CollectFn = int (*)(const MarlnavDims *, const MarlnavParams *, const MarlnavStepBuffers *,
+                          uint64_t, const MarlnavPolicyDims *, const MarlnavPolicyBuffers *,
+                          uint64_t, uint64_t, const MarlnavRolloutBuffers *, int64_t, double,
+                          void *);
 
 struct OutSet {
     PyObject *obs = nullptr;          // _PackedObservations
@@ -481,6 +485,80 @@ PyObject *Engine_launch(Engine *e, PyObject *args)
     return do_launch(e, (const void *)act, fp, extra);
 }
 
+// rollout(fn, pdims, pbufs, rbufs, obs_ptr, obs_norm_ptr, T, policy_seed,
+// policy_step_idx0, gamma): T steps of the env under a policy as ONE call of
+// marlnav_rollout_collect (fn: its address; the three structs as bytes-like
+// objects, abi.py) on the current stream, with this engine's dims, parameters
+// and state buffers. obs_ptr / obs_norm_ptr: (P, A, D) device buffers for the
+// raw observations and for the normalised ones of the last step. Leaves the
+// engine as T step() calls leave it: the step counters advanced by T, the
+// state buffers swapped after an odd T; the previous step's outputs are no
+// longer "the last step" (Env._reinit_mask is set by the caller).
+PyObject *Engine_rollout(Engine *e, PyObject *args)
+{
+    unsigned long long fn_addr, obs_ptr, norm_ptr, seed, pidx;
+    long long T;
+    double gamma;
+    PyObject *pd, *pb, *rb;
+    if (!PyArg_ParseTuple(args, "KOOOKKLKKd", &fn_addr, &pd, &pb, &rb, &obs_ptr, &norm_ptr, &T,
+                          &seed, &pidx, &gamma))
+        return nullptr;
+    MarlnavPolicyDims pdims;
+    MarlnavPolicyBuffers pbufs;
+    MarlnavRolloutBuffers rbufs;
+    if (!read_struct(pd, &pdims, sizeof pdims, "policy dims") ||
+        !read_struct(pb, &pbufs, sizeof pbufs, "policy buffers") ||
+        !read_struct(rb, &rbufs, sizeof rbufs, "rollout buffers"))
+        return nullptr;
+    if (!fn_addr || !e->fast_ok) {
+        PyErr_SetString(PyExc_RuntimeError,
+                        "rollout needs the engine's fast path: native re-init, the default init "
+                        "sampler and parameters in sync");
+        return nullptr;
+    }
+    void *stream = nullptr;
+    if (!current_stream(e, &stream)) return nullptr;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) {
+        (void)hipGetLastError();
+        cap = hipStreamCaptureStatusNone;
+    }
+    const bool capturing = cap == hipStreamCaptureStatusActive;
+    if (capturing && !e->allow_capture) {
+        PyErr_SetString(PyExc_RuntimeError,
+                        "a rollout under stream capture replays its steps' re-init draws (and the "
+                        "policy's normals) on every graph replay; set env.allow_graph_capture = "
+                        "True to accept that (timing runs)");
+        return nullptr;
+    }
+    if (capturing && e->base.states_out && e->held[kStatesAlt]) {
+        PyErr_SetString(PyExc_RuntimeError,
+                        "a rollout under stream capture is not supported with double-buffered "
+                        "states (states_double_buffer=True): the buffer swap happens on the host");
+        return nullptr;
+    }
+    MarlnavStepBuffers b = e->base;
+    b.obs = (float *)(uintptr_t)obs_ptr;
+    b.obs_norm = (float *)(uintptr_t)norm_ptr;
+    b.fresh_states = b.fresh_obstacles = b.fresh_target = nullptr;
+    MarlnavParams p = e->params;
+    p.flags &= ~(uint32_t)(MARLNAV_FRESH_STATES_FROM_MOVED | MARLNAV_WRITE_OBS_NORM);
+    if (b.norm_mean && b.norm_scale) p.flags |= MARLNAV_WRITE_OBS_NORM;  // a normaliser is attached
+    const int rc = reinterpret_cast<CollectFn>(fn_addr)(&e->dims, &p, &b, e->step_idx, &pdims,
+                                                        &pbufs, seed, pidx, &rbufs, T, gamma,
+                                                        stream);
+    if (rc) return raise_step_error(e, rc);
+    if ((T & 1) && b.states_out && e->held[kStatesAlt]) {
+        std::swap(e->held[kStates], e->held[kStatesAlt]);
+        std::swap(e->held_st[kStates], e->held_st[kStatesAlt]);
+        std::swap(e->base.states, e->base.states_out);
+    }
+    e->step_idx += (unsigned long long)T;
+    e->steps_done += (unsigned long long)T;
+    forget_last(e);
+    Py_RETURN_NONE;
+}
+
 // track_state(states, obstacles, target, step_num, terminates, states_alt):
 // the Env's current tensors; states_alt (or None) is the buffer the next step
 // writes the new states into (MarlnavStepBuffers.states_out), after which
@@ -571,6 +649,9 @@ PyMethodDef Engine_methods[] = {
      "configure(dims, params, buffers, fast_ok)"},
     {"launch", (PyCFunction)Engine_launch, METH_VARARGS,
      "launch(actions_ptr, fresh_ptrs|None, extra_flags) -> (obs, reward, terminated, truncated)"},
+    {"rollout", (PyCFunction)Engine_rollout, METH_VARARGS,
+     "rollout(collect_fn, policy_dims, policy_bufs, rollout_bufs, obs_ptr, obs_norm_ptr, T, "
+     "policy_seed, policy_step_idx0, gamma): T steps under a policy as one C call"},
     {"reset_pool", (PyCFunction)Engine_reset_pool, METH_NOARGS, "drop every pooled output set"},
     {"track_state", (PyCFunction)Engine_track_state, METH_VARARGS,
      "track_state(states, obstacles, target, step_num, terminates, states_alt|None): the tensors a "

@@ -7,8 +7,16 @@
 // float64 as the reference accumulates (torch.zeros(P, dtype=float)). Mean
 // and unbiased std are two-pass block reductions in a fixed order, so results
 // are deterministic run to run.
+//
+// marlnav_rollout_collect: the whole of MAPPO.get_data (models.py:106-125) as
+// one host call that enqueues the existing observe / policy / step launches
+// back to back, each step kernel writing its normalised observations straight
+// into the next row of the stacked rollout storage. Two small kernels of its
+// own: the ObsNormalizer of row 0 (the later rows come normalised out of the
+// step kernels) and the merge of the terminated / truncated flag stacks.
 #include <hip/hip_runtime.h>
 
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -108,6 +116,83 @@ __global__ void __launch_bounds__(kThreads) normalize_kernel(double *__restrict_
 
 int64_t blocks_for(int64_t P) { return (P + kThreads - 1) / kThreads; }
 
+// ObsNormalizer (utils.py:519-532) of packed (P, A, D) observations: one IEEE
+// subtraction and one IEEE division per element, the step kernels' fused
+// normaliser (kernel_block.h) on row 0 of a rollout. One thread per element.
+__global__ void __launch_bounds__(kThreads) obs_norm_kernel(const float *__restrict__ obs,
+                                                             const float *__restrict__ mean,
+                                                             const float *__restrict__ scale,
+                                                             int64_t n, int D,
+                                                             float *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const int k = (int)(i % D);
+    out[i] = (obs[i] - mean[k]) / scale[k];
+}
+
+// bytes 0 / 1 of (a | b) != 0 for the four (eight) bytes of a word: every
+// byte's bits are or-ed down into its bit 0
+__device__ __forceinline__ uint32_t any_bits(uint32_t x)
+{
+    x |= x >> 4;
+    x |= x >> 2;
+    x |= x >> 1;
+    return x & 0x01010101u;
+}
+
+// done[i] = (done[i] | trunc[i]) != 0 over n bytes (models.py:117 for a whole
+// rollout). The first `head` bytes, up to done's 16-byte boundary, and the
+// last n - head - 16 nvec one at a time, the nvec pieces between as 16-byte
+// vectors; the host passes head = n (nvec = 0) when the two pointers are not
+// equally placed within 16 bytes. One thread per piece or single byte.
+__global__ void __launch_bounds__(kThreads) merge_flags_kernel(uint8_t *__restrict__ done,
+                                                                const uint8_t *__restrict__ trunc,
+                                                                int64_t n, int64_t head,
+                                                                int64_t nvec)
+{
+    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (g < nvec) {
+        uint4 a = *reinterpret_cast<const uint4 *>(done + head + 16 * g);
+        const uint4 b = *reinterpret_cast<const uint4 *>(trunc + head + 16 * g);
+        a.x = any_bits(a.x | b.x);
+        a.y = any_bits(a.y | b.y);
+        a.z = any_bits(a.z | b.z);
+        a.w = any_bits(a.w | b.w);
+        *reinterpret_cast<uint4 *>(done + head + 16 * g) = a;
+        return;
+    }
+    const int64_t k = g - nvec;                       // k-th single byte
+    const int64_t i = k < head ? k : k + 16 * nvec;   // head bytes, then the tail
+    if (i >= n) return;
+    done[i] = (done[i] | trunc[i]) != 0;
+}
+
+int failf(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+int failf(int code, const char *fmt, ...)
+{
+    char msg[400];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(msg, sizeof(msg), fmt, ap);
+    va_end(ap);
+    return marlnav_internal_fail(code, msg);
+}
+
+// a launch of step t failed inside `what`: its message, with the step named
+int fail_step(int code, int64_t t, const char *what)
+{
+    char inner[256];
+    snprintf(inner, sizeof(inner), "%s", marlnav_last_error());
+    return failf(code, "marlnav_rollout_collect: step %lld, %s: %s", (long long)t, what, inner);
+}
+
+bool overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
 }  // namespace
 
 extern "C" {
@@ -135,6 +220,174 @@ int marlnav_discounted_returns(const float *rewards, const uint8_t *done, int64_
     hipLaunchKernelGGL(normalize_kernel, grid, blk, 0, s, returns, T, P, stats);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
+    return 0;
+}
+
+int marlnav_rollout_collect(const MarlnavDims *dims, const MarlnavParams *params,
+                            const MarlnavStepBuffers *env, uint64_t env_step_idx0,
+                            const MarlnavPolicyDims *pdims, const MarlnavPolicyBuffers *policy,
+                            uint64_t policy_seed, uint64_t policy_step_idx0,
+                            const MarlnavRolloutBuffers *rollout, int64_t T, double gamma,
+                            void *stream)
+{
+    constexpr int64_t kMaxSteps = (int64_t)1 << 20;
+    // ---- everything is checked before the first launch
+    if (!dims || !params || !env || !pdims || !policy || !rollout)
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: %s is NULL",
+                     !dims ? "dims" : !params ? "params" : !env ? "env" : !pdims ? "pdims"
+                     : !policy ? "policy" : "rollout");
+    if (T < 1 || T > kMaxSteps)
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: T=%lld outside [1, %lld]",
+                     (long long)T, (long long)kMaxSteps);
+    if (marlnav_counter_slots(dims) < 0) return MARLNAV_EINVAL;  // (the message names the field)
+    const int64_t P = dims->num_parallel;
+    const int A = dims->num_agents;
+    const int D = 2 + 2 * dims->num_obstacles + 2 * (A - 1);
+    if (pdims->num_agents != A)
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: policy num_agents=%d, env %d",
+                     pdims->num_agents, A);
+    if (pdims->obs_dim != D)
+        return failf(MARLNAV_EINVAL,
+                     "marlnav_rollout_collect: policy obs_dim=%d, the env's rows have "
+                     "2 + 2*O + 2*(A-1) = %d", pdims->obs_dim, D);
+    if (pdims->num_parallel != P)
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: policy num_parallel=%lld, env %lld",
+                     (long long)pdims->num_parallel, (long long)P);
+    if (pdims->env_offset != dims->env_offset || dims->env_offset < 0)
+        return failf(MARLNAV_EINVAL,
+                     "marlnav_rollout_collect: policy env_offset=%lld, env %lld (equal and >= 0)",
+                     (long long)pdims->env_offset, (long long)dims->env_offset);
+    if (pdims->hidden_size < 1 || pdims->hidden_size > 512)
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: policy hidden_size=%d outside "
+                     "[1, 512]", pdims->hidden_size);
+    if (pdims->reserved != 0)
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: policy reserved=%d must be 0",
+                     pdims->reserved);
+    if (!(params->flags & MARLNAV_WRITE_OBS_NORM))
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: params->flags lacks "
+                     "MARLNAV_WRITE_OBS_NORM (the policy reads the steps' normalised observations)");
+    if (!(params->flags & MARLNAV_SCALE_ACTIONS))
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: params->flags lacks "
+                     "MARLNAV_SCALE_ACTIONS (the steps read the policy-scale actions)");
+    if (env->fresh_states)
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: fresh_states is given: re-init "
+                     "from the reference's RNG needs the host every step (native re-init only)");
+#define MARLNAV_NEED(s, f) \
+    if (!(s)->f) return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: " #s "->" #f " is NULL")
+    MARLNAV_NEED(env, states);
+    MARLNAV_NEED(env, obstacles);
+    MARLNAV_NEED(env, target);
+    MARLNAV_NEED(env, step_num);
+    MARLNAV_NEED(env, terminates);
+    MARLNAV_NEED(env, formation);
+    MARLNAV_NEED(env, obs);
+    MARLNAV_NEED(env, obs_norm);
+    MARLNAV_NEED(env, norm_mean);
+    MARLNAV_NEED(env, norm_scale);
+    MARLNAV_NEED(policy, actor_fc1_w);
+    MARLNAV_NEED(policy, actor_fc1_b);
+    MARLNAV_NEED(policy, actor_mu_w);
+    MARLNAV_NEED(policy, actor_mu_b);
+    MARLNAV_NEED(policy, actor_std_w);
+    MARLNAV_NEED(policy, actor_std_b);
+    MARLNAV_NEED(policy, critic_fc1_w);
+    MARLNAV_NEED(policy, critic_fc1_b);
+    MARLNAV_NEED(policy, critic_fc2_w);
+    MARLNAV_NEED(policy, critic_fc2_b);
+    MARLNAV_NEED(rollout, obs);
+    MARLNAV_NEED(rollout, actions);
+    MARLNAV_NEED(rollout, log_probs);
+    MARLNAV_NEED(rollout, values);
+    MARLNAV_NEED(rollout, rewards);
+    MARLNAV_NEED(rollout, done);
+    MARLNAV_NEED(rollout, truncated);
+#undef MARLNAV_NEED
+    const bool want_returns = rollout->returns || rollout->returns_stats || rollout->returns_work;
+    if (want_returns && (!rollout->returns || !rollout->returns_stats || !rollout->returns_work))
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: rollout->returns, returns_stats "
+                     "and returns_work must all be given or all be NULL");
+    if (reinterpret_cast<uintptr_t>(rollout->actions) & 7u)
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: rollout->actions must be 8-byte "
+                     "aligned");
+    const int64_t row_obs = P * A * D;  // floats of one observation row
+    const int64_t nflags = T * P;
+    const size_t state_bytes = (size_t)P * A * 5 * sizeof(float);
+    if (env->states_out && overlap(env->states, state_bytes, env->states_out, state_bytes))
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: env->states_out overlaps states");
+    if (overlap(rollout->obs, (size_t)T * row_obs * sizeof(float), env->obs_norm,
+                (size_t)row_obs * sizeof(float)))
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: rollout->obs overlaps "
+                     "env->obs_norm (the last step's observations would land in the stack)");
+    if (overlap(rollout->done, (size_t)nflags, rollout->truncated, (size_t)nflags))
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: rollout->truncated overlaps done");
+    // the merge: 16-byte pieces where done and truncated are equally placed
+    int64_t head = nflags, nvec = 0;
+    {
+        const uintptr_t d0 = reinterpret_cast<uintptr_t>(rollout->done);
+        if (((d0 ^ reinterpret_cast<uintptr_t>(rollout->truncated)) & 15u) == 0) {
+            head = (int64_t)((16 - (d0 & 15u)) & 15u);
+            if (head > nflags) head = nflags;
+            nvec = (nflags - head) / 16;
+        }
+    }
+    const int64_t merge_blocks = blocks_for(nvec + (nflags - 16 * nvec));
+    const int64_t norm_blocks = blocks_for(row_obs);
+    if (merge_blocks > 0x7fffffff || norm_blocks > 0x7fffffff || P > ((int64_t)64 << 31) - 64)
+        return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: num_parallel=%lld (x T=%lld) too "
+                     "large", (long long)P, (long long)T);
+
+    // ---- row 0: the observations of the current state, normalised (models.py:110)
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = marlnav_observe(dims, params, env->states, env->obstacles, env->target, env->obs,
+                                 stream))
+        return fail_step(rc, 0, "marlnav_observe");
+    hipLaunchKernelGGL(obs_norm_kernel, dim3((unsigned)norm_blocks), dim3(kThreads), 0, s, env->obs,
+                       env->norm_mean, env->norm_scale, row_obs, D, rollout->obs);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        return failf(MARLNAV_ELAUNCH, "marlnav_rollout_collect: step 0, normaliser: %s",
+                     hipGetErrorString(e));
+
+    // ---- the steps (models.py:113-124)
+    MarlnavPolicyBuffers pb = *policy;
+    pb.eps_out = nullptr;
+    MarlnavStepBuffers sb = *env;
+    sb.fresh_states = sb.fresh_obstacles = sb.fresh_target = nullptr;
+    for (int64_t t = 0; t < T; ++t) {
+        pb.obs_norm = rollout->obs + t * row_obs;
+        pb.eps = rollout->eps ? rollout->eps + t * P * A * 2 : nullptr;
+        pb.actions = rollout->actions + t * P * A * 2;
+        pb.log_probs = rollout->log_probs + t * P * A;
+        pb.values = rollout->values + t * P;
+        if (int rc = marlnav_policy_act(pdims, &pb, policy_seed, policy_step_idx0 + (uint64_t)t,
+                                        stream))
+            return fail_step(rc, t, "marlnav_policy_act");
+        sb.actions = pb.actions;
+        sb.reward = rollout->rewards + t * P;
+        sb.terminated = rollout->done + t * P;
+        sb.truncated = rollout->truncated + t * P;
+        sb.obs_norm = t + 1 < T ? rollout->obs + (t + 1) * row_obs : env->obs_norm;
+        if (int rc = marlnav_step(dims, params, &sb, env_step_idx0 + (uint64_t)t, stream))
+            return fail_step(rc, t, "marlnav_step");
+        if (sb.states_out) {  // the step wrote the new states there: current from here on
+            float *cur = sb.states_out;
+            sb.states_out = sb.states;
+            sb.states = cur;
+        }
+    }
+
+    // ---- done = terminated | truncated over the whole stack (models.py:117)
+    hipLaunchKernelGGL(merge_flags_kernel, dim3((unsigned)merge_blocks), dim3(kThreads), 0, s,
+                       rollout->done, rollout->truncated, nflags, head, nvec);
+    e = hipGetLastError();
+    if (e != hipSuccess)
+        return failf(MARLNAV_ELAUNCH, "marlnav_rollout_collect: after step %lld, flag merge: %s",
+                     (long long)(T - 1), hipGetErrorString(e));
+    if (want_returns)
+        if (int rc = marlnav_discounted_returns(rollout->rewards, rollout->done, T, P, gamma,
+                                                rollout->returns, rollout->returns_stats,
+                                                rollout->returns_work, stream))
+            return fail_step(rc, T - 1, "marlnav_discounted_returns after it");
     return 0;
 }
 

@@ -290,7 +290,7 @@ class Env(object):
         self.__dict__['_states_t'] = None
         del st, alt
 
-    def _unshare_state(self):
+    def _unshare_state(self, multi_step=False):
         """Copy-on-write of the tensors a step writes in place. The
         reference's re-init rebinds `states`, `obstacles`, `target` and
         `_step_num` to new tensors (environment.py:79-83) and `_terminates` at
@@ -302,12 +302,17 @@ class Env(object):
         when the engine reports one of them referenced outside the Env, the
         Env moves to a copy (stream-ordered) before the step, and a held
         second states buffer is replaced. Returns (held pre-step `states` or
-        None, held pre-step `_step_num` or None) for `_finish_held`."""
+        None, held pre-step `_step_num` or None) for `_finish_held`.
+
+        ``multi_step``: the call that follows runs several steps
+        (``rollout.collect_fused``), so a held current `states` is copied
+        even when double-buffered (the second step would write it); holders
+        then keep the pre-call values, with no `_finish_held`."""
         shared = self._engine.shared_state()
         held = held_sn = None
         if shared[0]:
             held = self._states
-            if not self.__dict__.get('_double_buffer', False):
+            if multi_step or not self.__dict__.get('_double_buffer', False):
                 # in place: the Env steps a copy
                 object.__setattr__(self, '_states', held.clone())
             # double-buffered, the step reads the current buffer and writes

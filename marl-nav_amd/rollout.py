@@ -19,6 +19,9 @@ as one HIP scan instead of a Python loop of T x 3 small tensor ops.
   parameter tensors.
 * ``collect(env, policy, buffer)`` - the ``get_data`` loop (models.py:106-125)
   around ``Env.step`` with no ``torch.nn`` / ``torch.distributions`` call in it.
+* ``collect_fused(env, policy, buffer)`` - the same rollout enqueued by one C
+  call (libmarlnav.so ``marlnav_rollout_collect``): the step kernels write
+  their normalised observations straight into the buffer's rows.
 * ``FusedPPO(actor, critic, epsilon, ent_const)`` - ``MAPPO._actor_loss`` /
   ``_critic_loss`` (models.py:270-316) of one minibatch with the gradient of
   every parameter written to ``.grad`` (libmarlnav.so
@@ -339,6 +342,103 @@ def collect(env, policy, buffer, eps_source=None, gamma=0.9):
     stats = {"trunc": trunc, "col": col, "tar": tar}
     env._num_trunc = env._num_col = env._num_tar = 0      # models.py:153-158
     return mean, stats
+
+
+def collect_fused(env, policy, buffer, eps=None, gamma=0.9):
+    """``collect`` as ONE C call (libmarlnav.so ``marlnav_rollout_collect``):
+    the initial observations and their normalisation, then for each of the
+    ``buffer.buffer_len`` steps the policy launch and the step launch, the
+    merge ``done = terminated | truncated`` over the whole stack and the
+    returns scan are enqueued back to back on the current stream, with no
+    Python, no ``torch`` launch and no copy between them. Every step kernel
+    writes its normalised observations straight into the buffer's next row,
+    where the next policy launch reads them. The buffer, ``buffer.returns``,
+    the env and the policy end exactly as ``collect`` leaves them, bit for
+    bit (the same kernels on the same bits); returns the same
+    ``(mean_rew, {'trunc', 'col', 'tar'})``.
+
+    ``eps``: None for the policy kernel's own stream (``policy.step_idx``
+    then advances by the number of steps), or a ``(T, P*A, 2)`` float32
+    tensor of standard normals, row ``t`` for step ``t``.
+
+    Tensors the caller still holds from before the call (``env.states``,
+    ``obstacles``, ``target``, ``_step_num``, ``_terminates``) are not
+    written: the env moves to copies first, and the held ones keep their
+    pre-call values.
+
+    Raises RuntimeError, before anything is launched, for what only the
+    per-step loop of ``collect`` can do: an env in reference-RNG mode or with
+    a user-assigned init sampler (the host draws every step), no attached
+    normaliser or action scaler, parameters that cannot be synced; and under
+    stream capture unless ``env.allow_graph_capture`` is set (then the
+    episode counters are left alone and the stats are None: reading them
+    would synchronise)."""
+    who = "collect_fused"
+    if env._rng != 'native' or env._init_sampler is not env._default_init_sampler:
+        raise RuntimeError(f"{who} needs an env in native-RNG mode with its default init "
+                           "sampler: a reference-RNG or user-assigned sampler is called on the "
+                           "host every step; use collect() for such an env")
+    if env._normalizer is None or env._action_scaler is None:
+        raise RuntimeError(f"{who} needs env.attach_normalizer(...) and "
+                           "env.attach_action_scaler(...), as collect() does: the policy reads "
+                           "normalised observations and the env takes policy-scale actions")
+    dev = env.device
+    capturing = torch.cuda.is_current_stream_capturing()
+    if capturing and not env.allow_graph_capture:
+        raise RuntimeError(f"{who} under stream capture replays the steps' re-init draws on "
+                           "every graph replay; set env.allow_graph_capture = True to accept "
+                           "that (timing runs), or use collect() outside the capture")
+    P, A, D = env._obs_shape
+    if (A, D) != (policy.num_agents, policy.obs_dim):
+        raise ValueError(f"policy is built for {policy.num_agents} agents x {policy.obs_dim} "
+                         f"features, the env has {A} x {D}")
+    if policy.device != dev:
+        raise ValueError(f"the policy is on {policy.device}, the env on {dev}")
+    T = buffer.buffer_len
+    if eps is not None and (eps.dtype != torch.float32 or eps.device != dev
+                            or tuple(eps.shape) != (T, P * A, 2) or not eps.is_contiguous()):
+        raise ValueError(f"eps: need a contiguous float32 {(T, P * A, 2)} tensor on {dev}, got "
+                         f"{eps.dtype} {tuple(eps.shape)} on {eps.device}")
+    env._sync_params()
+    if any(env._engine.shared_state()):
+        env._unshare_state(multi_step=True)
+    if not env._engine.fast_ok:
+        raise RuntimeError(f"{who}: the env's parameters are not in sync with its engine and "
+                           "could not be synced; use collect()")
+    lib = abi.load_library()
+    buffer.reserve(P, A, D, dev)
+    buffer.clear()
+    r = abi.MarlnavRolloutBuffers()
+    for name, s in zip(abi.ROLLOUT_BUFFER_FIELDS, buffer._store):
+        setattr(r, name, s.data_ptr())
+    truncated = torch.empty(T, P, dtype=torch.uint8, device=dev)
+    returns = torch.empty(T, P, dtype=_F64, device=dev)
+    stats = torch.empty(2, dtype=_F64, device=dev)
+    work = torch.empty(int(lib.marlnav_returns_work_size(P)), dtype=_F64, device=dev)
+    # the env's own observation outputs: the raw rows of every step and the
+    # normalised ones of the last step (the earlier ones land in the buffer)
+    raw, last = env._new_obs(), env._new_obs()
+    r.truncated, r.eps = truncated.data_ptr(), None if eps is None else eps.data_ptr()
+    r.returns, r.returns_stats, r.returns_work = returns.data_ptr(), stats.data_ptr(), work.data_ptr()
+    pd, pb = policy._dims, policy._bufs
+    for f, t in policy._params:
+        setattr(pb, f, t.data_ptr())
+    pd.num_parallel = P
+    env._engine.rollout(abi.fn_addr(lib.marlnav_rollout_collect), bytes(pd), bytes(pb), bytes(r),
+                        raw.data_ptr(), last.data_ptr(), T, policy.seed, policy.step_idx,
+                        float(gamma))
+    del truncated, work, raw, last     # stream-ordered: reused after the kernels
+    if eps is None:
+        policy.step_idx += T
+    buffer.commit(T)
+    buffer.returns = returns
+    env._reinit_mask = torch.where(buffer.stacked(buffer.DONE)[T - 1], 1, 0)   # environment.py:102
+    mean = stats[0]
+    if capturing:
+        return mean, None
+    trunc, col, tar = env._counter_totals()                # one read of the three counters
+    env._num_trunc = env._num_col = env._num_tar = 0      # models.py:153-158
+    return mean, {"trunc": trunc, "col": col, "tar": tar}
 
 
 def minibatch_bounds(buffer_len, batch_size):
