@@ -1,8 +1,8 @@
 /*
  * marlnav.h - C ABI of the MI355X (gfx950) environment-step library
  * (libmarlnav.so, built from marl-nav_amd/csrc/marlnav_step.hip,
- * marlnav_rollout.hip, marlnav_policy.hip, marlnav_ppo.hip and
- * marlnav_adam.hip).
+ * marlnav_rollout.hip, marlnav_policy.hip, marlnav_ppo.hip,
+ * marlnav_adam.hip and marlnav_eval.hip).
  *
  * The reference (JussiM01/MARL-nav) has no FFI: its boundary is the Python
  * class `Env` (marlnav/environment.py:8-286). Each entry point below replaces
@@ -312,6 +312,102 @@ int marlnav_rollout_collect(const MarlnavDims *dims, const MarlnavParams *params
                             uint64_t policy_seed, uint64_t policy_step_idx0,
                             const MarlnavRolloutBuffers *rollout, int64_t T, double gamma,
                             void *stream);
+
+/* marlnav_actor_act modes */
+#define MARLNAV_ACT_MEAN   0  /* actions = dist.loc (animation.py:48)      */
+#define MARLNAV_ACT_SAMPLE 1  /* actions = dist.sample() (animation.py:46) */
+
+/* The actor half of marlnav_policy_act alone, as the reference's rendering
+ * path runs it (animation.py:40-50 with init_render :80-96, which loads only
+ * the actor's weights): Actor.forward (models.py:27-36) and then dist.loc
+ * (MARLNAV_ACT_MEAN: actions = tanh(fc_mu(fc1(x))), nothing else evaluated) or
+ * dist.sample() (MARLNAV_ACT_SAMPLE: mu + sqrt(v) * eps, bit-identical to
+ * marlnav_policy_act's actions for the same eps, or the same (policy_seed,
+ * step_idx, env_offset) with eps NULL). One launch.
+ * Reads obs_norm, the six actor tensors (live, nothing cached) and, in SAMPLE
+ * mode, eps; writes actions and, when given, eps_out (SAMPLE mode only). The
+ * four critic pointers, log_probs and values are ignored and may be NULL.
+ * Every action is a function of its own row only: the result does not depend
+ * on P, on the block a row lands in or on how envs are split into calls. */
+int marlnav_actor_act(const MarlnavPolicyDims *dims, const MarlnavPolicyBuffers *bufs,
+                      int mode, uint64_t policy_seed, uint64_t step_idx, void *stream);
+
+/* Device pointers of one evaluation of T steps of P envs
+ * (marlnav_rollout_evaluate). Contiguous; everything is written by the call,
+ * nothing needs initialising. */
+typedef struct MarlnavEvalBuffers {
+    /* scratch the steps run through */
+    float *obs_norm_a;         /* (P, A, D) normalised observations, even steps  */
+    float *obs_norm_b;         /* (P, A, D) odd steps (the two alternate)        */
+    float *actions;            /* (P, A, 2) policy-scale actions, 8-byte aligned */
+    float *reward;             /* (P,)  the last step's (environment.py:100)     */
+    uint8_t *terminated;       /* (P,)  bool, the last step's                    */
+    uint8_t *truncated;        /* (P,)  bool, the last step's                    */
+    /* per-env episode state: the episode under way at the end of the call */
+    double *cur_return;        /* (P,)  sum of its rewards so far                */
+    int32_t *cur_len;          /* (P,)  its steps so far                         */
+    uint8_t *whole;            /* (P,)  it started inside the call (or the env
+                                  entered the call with step_num == 0)          */
+    /* per-env results over the episodes that ended inside the call and were
+     * whole; an env that entered the call mid-episode closes a partial one */
+    int32_t *ep_count;         /* (P,)                                           */
+    double *ret_sum;           /* (P,)  sum of the episode returns               */
+    double *ret_sqsum;         /* (P,)  sum of their squares                     */
+    double *ret_min;           /* (P,)  +inf without an episode                  */
+    double *ret_max;           /* (P,)  -inf without an episode                  */
+    int64_t *len_sum;          /* (P,)  sum of the episode lengths               */
+    int32_t *partial_count;    /* (P,)  0 or 1                                   */
+    /* totals over the envs (one block, fixed order) */
+    int64_t *totals_i;         /* 3: episodes, partials, len_sum                 */
+    double *totals_f;          /* 4: ret_sum, ret_sqsum, min, max                */
+    /* optional record of env trace_env (all NULL when trace_env < 0): row 0
+     * the state before the first step (Animation.__init__), row t + 1 the
+     * state after step t, finished envs showing their fresh state */
+    float *trace_states;       /* (T+1, A, 5)                                    */
+    float *trace_obstacles;    /* (T+1, S, 2)                                    */
+    float *trace_target;       /* (T+1, 2)                                       */
+    float *trace_reward;       /* (T,)                                           */
+    uint8_t *trace_terminated; /* (T,)  bool                                     */
+    uint8_t *trace_truncated;  /* (T,)  bool                                     */
+    int64_t trace_env;         /* local env index in [0, P), or -1: no trace     */
+    int64_t reserved;          /* must be 0                                      */
+} MarlnavEvalBuffers;
+
+/* The reference's policy rendering loop (animation.py:40-71: normalise the
+ * observations, Actor.forward, dist.loc or dist.sample(), ActionScaler,
+ * Env.step) for T steps of one env shard without the drawing, with the
+ * episode figures an evaluation reports, enqueued on `stream` by one call
+ * with no host work between the launches:
+ *   marlnav_observe of the current state into env->obs and its normalised
+ *     form into obs_norm_a (as marlnav_rollout_collect's row 0);
+ *   the tracker's start: every per-env array zero, ret_min = +inf, ret_max =
+ *     -inf, whole[p] = (step_num[p] == 0); trace row 0;
+ *   for t = 0 .. T-1 what marlnav_actor_act enqueues in `mode` (SAMPLE: the
+ *     kernel's own normals at policy_step_idx0 + t) from the observations of
+ *     step t into `actions`, what marlnav_step enqueues at env_step_idx0 + t,
+ *     writing the other obs_norm buffer, then the tracker:
+ *       cur_return += (double)reward[p]; cur_len += 1;
+ *       if terminated[p] | truncated[p]  (the `done` of models.py:117):
+ *         whole[p] ? (ep_count += 1, ret_sum += cur_return,
+ *                     ret_sqsum += cur_return * cur_return (one product and
+ *                     one sum, rounded separately), len_sum += cur_len,
+ *                     min / max updated)
+ *                  : partial_count += 1;
+ *         cur_return = 0, cur_len = 0, whole = 1
+ *     and trace row t + 1, read from the state buffer that step wrote;
+ *   the totals. With no whole episode totals_f[2..3] stay +inf / -inf.
+ * Every per-env number is a function of its own env's rewards in step order.
+ * env, policy, pdims: as for marlnav_rollout_collect (native re-init, both
+ *   MARLNAV_WRITE_OBS_NORM and MARLNAV_SCALE_ACTIONS, the state buffers
+ *   swapping per step with states_out); env->obs_norm is not used, and of
+ *   `policy` only the six actor tensors are read.
+ * Everything is validated before the first launch (MARLNAV_EINVAL, the
+ * message names the field). A failing launch ends the call at once. */
+int marlnav_rollout_evaluate(const MarlnavDims *dims, const MarlnavParams *params,
+                             const MarlnavStepBuffers *env, uint64_t env_step_idx0,
+                             const MarlnavPolicyDims *pdims, const MarlnavPolicyBuffers *policy,
+                             int mode, uint64_t policy_seed, uint64_t policy_step_idx0,
+                             const MarlnavEvalBuffers *eval, int64_t T, void *stream);
 
 /* Shapes of one PPO minibatch: rows lo..hi of a stacked rollout, T = hi - lo
  * steps of P envs. N = T*P env rows, M = N*A agent rows in (t, p, a) order. */

@@ -6,8 +6,9 @@ The package directory is ``marl-nav_amd/``; import it as ``marlnav_amd``
 (the alias module at the repository root) or with
 ``importlib.import_module('marl-nav_amd')``.
 """
-from . import abi, rollout, shard
+from . import abi, evaluation, rollout, shard
 from .environment import Env
+from .evaluation import EvalResult, FusedActor, evaluate
 from .rollout import (FusedAdam, FusedPolicy, FusedPPO, RolloutBuffer, collect, collect_fused,
                       minibatch_bounds, train_actor, train_critic)
 from .utils import (ActionScaler, ConstantSampler, MockInitializer, MockSampler,
@@ -19,5 +20,6 @@ __all__ = ["Env", "Observations", "ObsNormalizer", "ActionScaler", "MockInitiali
            "TriangleIntitializer", "ConstantSampler", "MockSampler", "init_sampler",
            "action_sampler", "set_all_seeds", "set_env_params", "set_init_params",
            "set_sampler_params", "set_normalizer_params", "set_scaler_params", "default_args",
-           "abi", "rollout", "shard", "FusedPolicy", "RolloutBuffer", "collect",
-           "collect_fused", "FusedPPO", "FusedAdam", "minibatch_bounds", "train_actor", "train_critic"]
+           "abi", "rollout", "shard", "evaluation", "FusedPolicy", "RolloutBuffer", "collect",
+           "collect_fused", "FusedPPO", "FusedAdam", "minibatch_bounds", "train_actor", "train_critic",
+           "FusedActor", "EvalResult", "evaluate"]

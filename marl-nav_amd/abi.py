@@ -95,6 +95,32 @@ class MarlnavRolloutBuffers(ctypes.Structure):
     _fields_ = [(n, _P) for n in ROLLOUT_BUFFER_FIELDS]
 
 
+ACT_MEAN, ACT_SAMPLE = 0, 1
+# what marlnav_actor_act dereferences (eps / eps_out: optional, SAMPLE mode only)
+ACTOR_REQUIRED_FIELDS = ("obs_norm",) + POLICY_WEIGHT_FIELDS[:6] + ("actions",)
+
+EVAL_SCRATCH_FIELDS = ("obs_norm_a", "obs_norm_b", "actions", "reward", "terminated", "truncated")
+# per-env arrays of P with their torch dtype names, in the struct's order
+EVAL_ENV_FIELDS = (("cur_return", "float64"), ("cur_len", "int32"), ("whole", "uint8"),
+                   ("ep_count", "int32"), ("ret_sum", "float64"), ("ret_sqsum", "float64"),
+                   ("ret_min", "float64"), ("ret_max", "float64"), ("len_sum", "int64"),
+                   ("partial_count", "int32"))
+EVAL_TOTAL_FIELDS = ("totals_i", "totals_f")
+EVAL_TRACE_FIELDS = ("trace_states", "trace_obstacles", "trace_target", "trace_reward",
+                     "trace_terminated", "trace_truncated")
+EVAL_POINTER_FIELDS = (EVAL_SCRATCH_FIELDS + tuple(f for f, _ in EVAL_ENV_FIELDS)
+                       + EVAL_TOTAL_FIELDS + EVAL_TRACE_FIELDS)
+# (every pointer but the trace's must be given)
+# what marlnav_rollout_evaluate needs of the env's MarlnavStepBuffers
+EVAL_ENV_REQUIRED = ("states", "obstacles", "target", "step_num", "terminates", "formation",
+                     "obs", "norm_mean", "norm_scale")
+
+
+class MarlnavEvalBuffers(ctypes.Structure):
+    _fields_ = ([(n, _P) for n in EVAL_POINTER_FIELDS]
+                + [("trace_env", ctypes.c_int64), ("reserved", ctypes.c_int64)])
+
+
 class MarlnavPpoDims(ctypes.Structure):
     _fields_ = [("num_parallel", ctypes.c_int64),
                 ("num_steps", ctypes.c_int64),
@@ -141,7 +167,8 @@ class MarlnavAdamBuffers(ctypes.Structure):
 EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_formation_obs",
            "marlnav_counter_slots", "marlnav_counters_total",
            "marlnav_returns_work_size", "marlnav_discounted_returns", "marlnav_policy_act",
-           "marlnav_rollout_collect", "marlnav_ppo_work_size", "marlnav_ppo_actor_grad", "marlnav_ppo_critic_grad",
+           "marlnav_rollout_collect", "marlnav_actor_act", "marlnav_rollout_evaluate",
+           "marlnav_ppo_work_size", "marlnav_ppo_actor_grad", "marlnav_ppo_critic_grad",
            "marlnav_adam_state_size", "marlnav_adam_step",
            "marlnav_ppo_actor_update", "marlnav_ppo_critic_update",
            "marlnav_last_error", "marlnav_abi_version",
@@ -183,6 +210,16 @@ def _declare(lib):
                                             c.POINTER(MarlnavRolloutBuffers), c.c_int64, c.c_double,
                                             _P]
     lib.marlnav_rollout_collect.restype = c.c_int
+    lib.marlnav_actor_act.argtypes = [c.POINTER(MarlnavPolicyDims),
+                                      c.POINTER(MarlnavPolicyBuffers), c.c_int, c.c_uint64,
+                                      c.c_uint64, _P]
+    lib.marlnav_actor_act.restype = c.c_int
+    lib.marlnav_rollout_evaluate.argtypes = [dims_p, par_p, c.POINTER(MarlnavStepBuffers),
+                                             c.c_uint64, c.POINTER(MarlnavPolicyDims),
+                                             c.POINTER(MarlnavPolicyBuffers), c.c_int, c.c_uint64,
+                                             c.c_uint64, c.POINTER(MarlnavEvalBuffers), c.c_int64,
+                                             _P]
+    lib.marlnav_rollout_evaluate.restype = c.c_int
     ppo_dims_p, ppo_bufs_p = c.POINTER(MarlnavPpoDims), c.POINTER(MarlnavPpoBuffers)
     lib.marlnav_ppo_work_size.argtypes = [ppo_dims_p]
     lib.marlnav_ppo_work_size.restype = c.c_int64

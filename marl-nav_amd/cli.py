@@ -1,13 +1,20 @@
 """Command line of marlnav_amd, mirroring the reference's
 ``python -m marlnav`` (marlnav/__main__.py): same arguments and defaults.
 
-Implemented mode: the reward check (``-rc``, utils.py:579-666 via
+Implemented modes: the reward check (``-rc``, utils.py:579-666 via
 __main__.py:36-42) on the HIP environment step. Training (MAPPO) and
 rendering are the reference's own code and stay there: they take
 ``marlnav_amd.Env`` as their environment.
 
     python -m marlnav_amd -rc -se 0            # config-1 reward check
     python -m marlnav_amd -rc -sn 0 -ms 400    # mock scenario 0
+
+``--evaluate`` (marlnav_amd only) runs a trained actor on the device for
+``-ms`` steps (``marlnav_amd.evaluate``): what ``-re -sa policy -w FILE`` does
+per frame in the reference (animation.py:40-71), without the window, and
+prints the episode figures as one JSON line.
+
+    python -m marlnav_amd --evaluate -w weights/X_actor.pt -np 4096 -ms 1000
 """
 import argparse
 import sys
@@ -64,6 +71,13 @@ def build_parser():
       help="generator of the initializer's agent-noise draw: 'auto' = the env device, as "
            "the reference does on a GPU machine; 'cpu' = as on a CPU-only machine (the "
            "reference's CPU run, BASELINE configs[0])")
+    a('--evaluate', action='store_true',
+      help='run the actor of -w FILE for -ms steps on the device and print the episode '
+           'figures as one JSON line; -ra samples actions (default: the mean action), -pi '
+           'is the traced env of --trace-out and of the figure')
+    a('--trace-out', metavar='FILE.npz',
+      help='with --evaluate: save the traced env\'s states, obstacles, target, rewards and '
+           'flags of every step')
     a('--plot-dir', default='plots', help='directory of the saved figures')
     a('--no-plots', action='store_true', help='skip the figures, print the series')
     return p
@@ -75,11 +89,14 @@ def main(argv=None):
     import torch
     pkg = importlib.import_module("marl-nav_amd")
     args = build_parser().parse_args(argv)
+    if args.evaluate:
+        return _evaluate(pkg, args)
     if not args.reward_check:
         mode = 'rendering' if args.rendering else 'training'
         print(f"marlnav_amd implements the environment step; {mode} is the reference's "
               "own code (MAPPO / animation): run it with marlnav_amd.Env as its "
-              "environment (INTEGRATION.md). Use -rc for the reward check.",
+              "environment (INTEGRATION.md). Use -rc for the reward check, --evaluate to run "
+              "a trained actor without the window.",
               file=sys.stderr)
         return 2
     if not torch.cuda.is_available():
@@ -103,6 +120,74 @@ def main(argv=None):
     else:
         print(f"saved figures under {args.plot_dir}/")
     return 0
+
+
+def _evaluate(pkg, args):
+    """``--evaluate``: init_render's policy branch (animation.py:80-96) and
+    Animation.update's loop (:40-71) for ``-ms`` steps, as one call."""
+    import json
+
+    import torch
+    if not torch.cuda.is_available():
+        print("marlnav_amd needs a HIP device (no CPU fallback)", file=sys.stderr)
+        return 1
+    if not args.weights_file:
+        print("--evaluate needs the actor's weights: -w FILE (the reference's *_actor.pt)",
+              file=sys.stderr)
+        return 2
+    device = 'cuda'
+    if args.seed is not None:
+        pkg.set_all_seeds(args.seed)
+    env_params = pkg.set_env_params(args, device)
+    env_params['rng'] = 'native'           # the host is not in the loop: in-kernel re-init
+    if args.seed is not None:
+        env_params['seed'] = args.seed
+    env = pkg.Env(env_params)
+    env.attach_normalizer(pkg.ObsNormalizer(pkg.set_normalizer_params(args, device)))
+    env.attach_action_scaler(pkg.ActionScaler(pkg.set_scaler_params(args, device)))
+    actor = pkg.FusedActor.from_state_dict(
+        torch.load(args.weights_file, map_location='cpu', weights_only=True), device,
+        seed=args.seed or 0)
+    want_trace = bool(args.trace_out) or not args.no_plots
+    res = pkg.evaluate(env, actor, args.max_step, mode='sample' if args.random else 'mean',
+                       trace_env=args.parallel_index if want_trace else None)
+    print(json.dumps(res.as_dict()))
+    if res.trace is None:
+        return 0
+    trace = {k: v.cpu().numpy() for k, v in res.trace.items()}
+    if args.trace_out:
+        import numpy as np
+        np.savez(args.trace_out, **trace)
+    if not args.no_plots:
+        _plot_trace(trace, args)
+    return 0
+
+
+def _plot_trace(trace, args):
+    """One static figure of the traced env: every agent's path, the obstacles
+    and the target (the reference animates the same scatter, animation.py:
+    14-38), saved as check_rews saves its figures."""
+    import os
+    try:
+        import matplotlib
+        matplotlib.use('Agg')
+        import matplotlib.pyplot as plt
+    except ImportError:
+        return
+    fig, ax = plt.subplots(figsize=(args.fig_size_x, args.fig_size_y))
+    st = trace["states"]
+    for a in range(st.shape[1]):
+        ax.plot(st[:, a, 0], st[:, a, 1], lw=0.8, label=f"agent {a}")
+    ax.scatter(trace["obstacles"][:, :, 0], trace["obstacles"][:, :, 1], s=12, c='k',
+               label="obstacles")
+    ax.scatter(trace["target"][:, 0], trace["target"][:, 1], s=40, c='r', marker='*',
+               label="target")
+    ax.set_xlim(0, args.max_x_value)
+    ax.set_ylim(0, args.max_y_value)
+    ax.legend(loc='upper right', fontsize=7)
+    os.makedirs(args.plot_dir, exist_ok=True)
+    fig.savefig(os.path.join(args.plot_dir, f"evaluate_env_{args.parallel_index}.png"))
+    plt.close(fig)
 
 
 if __name__ == "__main__":

@@ -47,6 +47,9 @@ using CollectFn = int (*)(const MarlnavDims *, const MarlnavParams *, const Marl
                           uint64_t, const MarlnavPolicyDims *, const MarlnavPolicyBuffers *,
                           uint64_t, uint64_t, const MarlnavRolloutBuffers *, int64_t, double,
                           void *);
+using EvaluateFn = int (*)(const MarlnavDims *, const MarlnavParams *, const MarlnavStepBuffers *,
+                           uint64_t, const MarlnavPolicyDims *, const MarlnavPolicyBuffers *, int,
+                           uint64_t, uint64_t, const MarlnavEvalBuffers *, int64_t, void *);
 
 struct OutSet {
     PyObject *obs = nullptr;          // _PackedObservations
@@ -559,6 +562,77 @@ PyObject *Engine_rollout(Engine *e, PyObject *args)
     Py_RETURN_NONE;
 }
 
+// evaluate(fn, pdims, pbufs, ebufs, obs_ptr, T, mode, policy_seed,
+// policy_step_idx0): T steps of the env under the actor alone as ONE call of
+// marlnav_rollout_evaluate (fn: its address; the three structs as bytes-like
+// objects, abi.py) on the current stream: rollout()'s sibling, with the same
+// bookkeeping and the same capture rules. obs_ptr: a (P, A, D) device buffer
+// for the raw observations.
+PyObject *Engine_evaluate(Engine *e, PyObject *args)
+{
+    unsigned long long fn_addr, obs_ptr, seed, pidx;
+    long long T;
+    int mode;
+    PyObject *pd, *pb, *eb;
+    if (!PyArg_ParseTuple(args, "KOOOKLiKK", &fn_addr, &pd, &pb, &eb, &obs_ptr, &T, &mode, &seed,
+                          &pidx))
+        return nullptr;
+    MarlnavPolicyDims pdims;
+    MarlnavPolicyBuffers pbufs;
+    MarlnavEvalBuffers ebufs;
+    if (!read_struct(pd, &pdims, sizeof pdims, "policy dims") ||
+        !read_struct(pb, &pbufs, sizeof pbufs, "policy buffers") ||
+        !read_struct(eb, &ebufs, sizeof ebufs, "eval buffers"))
+        return nullptr;
+    if (!fn_addr || !e->fast_ok) {
+        PyErr_SetString(PyExc_RuntimeError,
+                        "evaluate needs the engine's fast path: native re-init, the default init "
+                        "sampler and parameters in sync");
+        return nullptr;
+    }
+    void *stream = nullptr;
+    if (!current_stream(e, &stream)) return nullptr;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess) {
+        (void)hipGetLastError();
+        cap = hipStreamCaptureStatusNone;
+    }
+    const bool capturing = cap == hipStreamCaptureStatusActive;
+    if (capturing && !e->allow_capture) {
+        PyErr_SetString(PyExc_RuntimeError,
+                        "an evaluation under stream capture replays its steps' re-init draws (and "
+                        "the actor's normals) on every graph replay; set env.allow_graph_capture = "
+                        "True to accept that (timing runs)");
+        return nullptr;
+    }
+    if (capturing && e->base.states_out && e->held[kStatesAlt]) {
+        PyErr_SetString(PyExc_RuntimeError,
+                        "an evaluation under stream capture is not supported with double-buffered "
+                        "states (states_double_buffer=True): the buffer swap happens on the host");
+        return nullptr;
+    }
+    MarlnavStepBuffers b = e->base;
+    b.obs = (float *)(uintptr_t)obs_ptr;
+    b.obs_norm = nullptr;
+    b.fresh_states = b.fresh_obstacles = b.fresh_target = nullptr;
+    MarlnavParams p = e->params;
+    p.flags &= ~(uint32_t)(MARLNAV_FRESH_STATES_FROM_MOVED | MARLNAV_WRITE_OBS_NORM);
+    if (b.norm_mean && b.norm_scale) p.flags |= MARLNAV_WRITE_OBS_NORM;  // a normaliser is attached
+    const int rc = reinterpret_cast<EvaluateFn>(fn_addr)(&e->dims, &p, &b, e->step_idx, &pdims,
+                                                         &pbufs, mode, seed, pidx, &ebufs, T,
+                                                         stream);
+    if (rc) return raise_step_error(e, rc);
+    if ((T & 1) && b.states_out && e->held[kStatesAlt]) {
+        std::swap(e->held[kStates], e->held[kStatesAlt]);
+        std::swap(e->held_st[kStates], e->held_st[kStatesAlt]);
+        std::swap(e->base.states, e->base.states_out);
+    }
+    e->step_idx += (unsigned long long)T;
+    e->steps_done += (unsigned long long)T;
+    forget_last(e);
+    Py_RETURN_NONE;
+}
+
 // track_state(states, obstacles, target, step_num, terminates, states_alt):
 // the Env's current tensors; states_alt (or None) is the buffer the next step
 // writes the new states into (MarlnavStepBuffers.states_out), after which
@@ -652,6 +726,9 @@ PyMethodDef Engine_methods[] = {
     {"rollout", (PyCFunction)Engine_rollout, METH_VARARGS,
      "rollout(collect_fn, policy_dims, policy_bufs, rollout_bufs, obs_ptr, obs_norm_ptr, T, "
      "policy_seed, policy_step_idx0, gamma): T steps under a policy as one C call"},
+    {"evaluate", (PyCFunction)Engine_evaluate, METH_VARARGS,
+     "evaluate(evaluate_fn, policy_dims, policy_bufs, eval_bufs, obs_ptr, T, mode, policy_seed, "
+     "policy_step_idx0): T steps under the actor alone as one C call"},
     {"reset_pool", (PyCFunction)Engine_reset_pool, METH_NOARGS, "drop every pooled output set"},
     {"track_state", (PyCFunction)Engine_track_state, METH_VARARGS,
      "track_state(states, obstacles, target, step_num, terminates, states_alt|None): the tensors a "

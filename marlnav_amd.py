@@ -6,7 +6,7 @@ import importlib as _importlib
 import sys as _sys
 
 _pkg = _importlib.import_module("marl-nav_amd")
-for _name in ("abi", "cli", "environment", "rollout", "shard", "utils"):
+for _name in ("abi", "cli", "environment", "evaluation", "rollout", "shard", "utils"):
     _sys.modules["marlnav_amd." + _name] = _importlib.import_module("marl-nav_amd." + _name)
 
 if __name__ == "__main__":
