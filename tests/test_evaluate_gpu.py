@@ -113,6 +113,23 @@ def test_sample_actions_are_the_policy_kernels(pkg, P, A, O, H, offset_floats):
     assert_bits_equal(np_(a1), np_(policy.act(obs, step_idx=1)[0]), "running counter")
 
 
+# (P, A, O, H) for the actor kernel alone (SHAPES also drives whole rollouts):
+# the advertised limits A = 64, O = 256 (D = 640, the widest row's LDS), and 16
+# agents over three policy blocks (the policy kernel's row loop makes 4 trips)
+LIMIT_SHAPES = [(65, 64, 256, 5), (130, 16, 32, 50)]
+
+
+@pytest.mark.parametrize("P,A,O,H", LIMIT_SHAPES)
+def test_sample_actions_are_the_policy_kernels_at_the_limits(pkg, P, A, O, H):
+    D = 2 + 2 * O + 2 * (A - 1)
+    obs = observations(P, A, D, 0)
+    policy, actor = make_policy(pkg, A, O, H, seed=11), make_actor(pkg, A, O, H, seed=11)
+    want = np_(policy.act(obs, step_idx=5)[0])
+    got = np_(actor.act(obs, mode='sample', step_idx=5))
+    assert got.shape == (P, A, 2) and np.isfinite(want).all() and np.unique(want).size > P * A
+    assert_bits_equal(got, want, "kernel normals, step 5")
+
+
 @pytest.mark.parametrize("offset_floats", [0, 2])
 @pytest.mark.parametrize("P,A,O,H", SHAPES)
 def test_mean_actions_are_the_policy_kernels_at_zero_noise(pkg, P, A, O, H, offset_floats):

@@ -10,7 +10,25 @@ absolute error must not exceed 4 x the reference's own largest fp32 error.
 The measured errors of both sides are printed to the terminal past pytest's
 capture (``capsys.disabled()``; tests/conftest.py owns the summary hook) and
 appended to the file named by MARLNAV_POLICY_PARITY_OUT, which is how
-profiles/policy_parity.txt was written."""
+profiles/policy_parity.txt was written.
+
+Generated shapes (tests/policy_ref.py ``SHAPES``, ``generated``): the truth is
+policy_ref in fp64 and the reference side policy_ref in fp32, both on the CPU,
+and each shape is held to the criterion on its own (``check_shape``: the
+reference side of a kind counts as at least 2^-24 x its largest fp64 entry).
+Which test reaches which path of marlnav_policy.hip:
+
+* the actor's row loop past its first trip, the generic critic above 3 envs,
+  every split of the hidden units (empty wave shares, every remainder of the
+  groups of 4 and 8, H = 512) and the limits A = 64, O = 256 (D = 640, 52 304 B
+  of LDS): test_parity_on_generated_shapes, against fp64;
+* compiled against generic variant: test_compiled_variant_equals_the_generic;
+* block and position independence: test_outputs_do_not_depend_on_position;
+* the ``relu`` that keeps a NaN and the clamp of the lanes past the last env:
+  test_nan_stays_in_its_own_rows;
+* the word-to-row mapping of the native normals (global row id with its high
+  word, the high word of step, the policy's key domain):
+  test_native_normals_equal_the_host_restatement."""
 import os
 from types import SimpleNamespace as NS
 
@@ -43,10 +61,10 @@ def run_case(pkg, c, **kw):
     return policy, w, obs, eps
 
 
-def report(capsys, title, pooled):
+def report(capsys, title, pooled, bound="reference"):
     """The pooled errors of both sides, on the terminal whatever the capture
     mode, and appended to $MARLNAV_POLICY_PARITY_OUT when that is set."""
-    text = "\n".join([f"{title} (largest |fp32 - fp64|, bound {pr.FACTOR:g} x reference)"]
+    text = "\n".join([f"{title} (largest |fp32 - fp64|, bound {pr.FACTOR:g} x {bound})"]
                      + ["  " + line for line in pooled.lines()])
     with capsys.disabled():
         print("\n" + text)
@@ -167,6 +185,155 @@ def test_env_offset_slice_equals_the_full_batch(native):
     assert_bits_equal(part[3], native.base[3][lo * NA_:(lo + n) * NA_], "eps_out")
     wrong = native.act(11, 5, env_offset=0, rows=slice(lo, lo + n))
     assert not np.array_equal(wrong[3], part[3])
+
+
+# ------------------------------------------------------------- generated shapes
+def on_device(pkg, shape, **kw):
+    """The generated case of ``shape`` (shared, on the CPU: left unchanged), a
+    FusedPolicy over device copies of its weights, and its obs and eps on the
+    device."""
+    c = pr.generated(*shape)
+    w = {k: v.to(DEV) for k, v in c.w.items()}
+    return c, pkg.FusedPolicy(*modules(w), **kw), c.obs.to(DEV), c.eps.to(DEV)
+
+
+def act_np(policy, obs, eps):
+    return [np_(o) for o in policy.act(obs, eps=eps)]
+
+
+def at_offset(t, offset_floats):
+    """A contiguous copy of ``t`` at ``offset_floats`` floats into a fresh
+    allocation: 0 is 16-byte aligned, 2 only 8-byte."""
+    flat = torch.empty(t.numel() + 4, device=DEV)
+    v = flat[offset_floats:offset_floats + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4 * offset_floats
+    return v
+
+
+@pytest.mark.parametrize("shape", pr.SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_parity_on_generated_shapes(pkg, capsys, shape):
+    """The criterion on each generated shape alone (``pr.check_shape``), all
+    three outputs against policy_ref in fp64; eps_out is eps bit for bit."""
+    c, policy, obs, eps = on_device(pkg, shape)
+    P, A = shape[:2]
+    eps_out = torch.empty(P * A, 2, device=DEV)
+    out = policy.act(obs, eps=eps, eps_out=eps_out)
+    assert out[0].shape == (P, A, 2) and out[1].shape == (P * A,) and out[2].shape == (P, 1)
+    assert_bits_equal(np_(eps_out), c.eps.numpy(), "eps_out")
+    chk = pr.check_shape(c.c64, c.ref32, [np_(o) for o in out])
+    report(capsys, f"parity, generated (P, A, O, H) = {shape}:", chk,
+           bound="max(reference, floor)")
+    assert not chk.failures(), chk.failures()
+
+
+@pytest.mark.parametrize("shape", [(129, 3, 8, 67), (70, 3, 3, 50)])
+def test_compiled_variant_equals_the_generic(pkg, shape):
+    """The compiled A3 O8 / A3 O3 kernels (16-byte aligned obs) and the
+    generic one (the same rows 8 bytes further): the load widths do not change
+    the arithmetic, so all three outputs agree bit for bit."""
+    c, policy, obs, eps = on_device(pkg, shape)
+    compiled = act_np(policy, at_offset(obs, 0), eps)
+    generic = act_np(policy, at_offset(obs, 2), eps)
+    for a, b, kind in zip(compiled, generic, pr.KINDS):
+        assert np.isfinite(a).all(), kind
+        assert_bits_equal(b, a, f"{shape} generic vs compiled {kind}")
+
+
+@pytest.mark.parametrize("shape", [(130, 16, 32, 50), (129, 3, 8, 67)])
+def test_outputs_do_not_depend_on_position(pkg, shape):
+    """Every output element is a function of its own row / env: a permutation
+    of the envs (obs and eps rows moved together) permutes the outputs, and an
+    env run alone (P = 1) gives its rows of the full run, bit for bit."""
+    c, policy, obs, eps = on_device(pkg, shape)
+    P, A = shape[:2]
+    full = act_np(policy, obs, eps)
+    perm = torch.randperm(P, generator=torch.Generator().manual_seed(17))
+    assert not torch.equal(perm, torch.arange(P))
+    moved = act_np(policy, obs[perm.to(DEV)].contiguous(),
+                   eps.view(P, A, 2)[perm.to(DEV)].reshape(P * A, 2).contiguous())
+    p = perm.numpy()
+    assert_bits_equal(moved[0], full[0][p], "permuted actions")
+    assert_bits_equal(moved[1].reshape(P, A), full[1].reshape(P, A)[p], "permuted log_probs")
+    assert_bits_equal(moved[2], full[2][p], "permuted values")
+    for e in (0, 63, 64, P - 1):
+        alone = act_np(policy, obs[e:e + 1].clone(), eps[e * A:(e + 1) * A].clone())
+        assert_bits_equal(alone[0], full[0][e:e + 1], f"env {e} alone: actions")
+        assert_bits_equal(alone[1], full[1][e * A:(e + 1) * A], f"env {e} alone: log_probs")
+        assert_bits_equal(alone[2], full[2][e:e + 1], f"env {e} alone: values")
+
+
+@pytest.mark.parametrize("shape", [(130, 16, 32, 50), (129, 3, 8, 67)])
+def test_nan_stays_in_its_own_rows(pkg, shape):
+    """One NaN feature of agent 1 of env 64: that agent's actions and log-prob
+    and that env's value are NaN (the critic's relu keeps a NaN), as
+    policy_ref gives them, and every other output element keeps its bits."""
+    c, policy, obs, eps = on_device(pkg, shape)
+    P, A = shape[:2]
+    clean = act_np(policy, obs, eps)
+    bad = obs.clone()
+    bad[64, 1, 3] = float("nan")
+    got = act_np(policy, bad, eps)
+    w = {f"{m}.{layer}.{attr}": getattr(getattr(mod, layer), attr)
+         for m, mod in (("actor", policy.actor), ("critic", policy.critic))
+         for layer in (("fc1", "fc_mu", "fc_std") if m == "actor" else ("fc1", "fc2"))
+         for attr in ("weight", "bias")}
+    ref = [np_(o) for o in pr.policy_ref(w, bad, eps)]
+    want = [np.zeros((P, A, 2), bool), np.zeros(P * A, bool), np.zeros((P, 1), bool)]
+    want[0][64, 1], want[1][64 * A + 1], want[2][64] = True, True, True
+    for g, r, m, cl, kind in zip(got, ref, want, clean, pr.KINDS):
+        assert np.isfinite(cl).all(), kind
+        np.testing.assert_array_equal(np.isnan(g), m, f"{kind}: the kernel's NaN mask")
+        np.testing.assert_array_equal(np.isnan(r), m, f"{kind}: policy_ref's NaN mask")
+        assert_bits_equal(g[~m], cl[~m], f"{kind} outside the NaN rows")
+
+
+# (P, A, O, H, seed, step, env_offset)
+NORMALS = {"300x3x3": (300, 3, 3, 50, 11, 5, 0),
+           "high_words_of_seed_and_step": (300, 3, 3, 50, 11 + 2 ** 32, 5 + 2 ** 32, 0),
+           "70x16x32": (70, 16, 32, 50, 11, 5, 0),
+           "gid_crosses_2^32": (300, 3, 3, 50, 11, 5, 2 ** 32 // 3 - 100)}
+NORMALS_BOUND = 1e-4
+
+
+@pytest.mark.parametrize("name", list(NORMALS))
+def test_native_normals_equal_the_host_restatement(pkg, capsys, name):
+    """eps_out of the kernel's own draw against tests/policy_ref.py
+    ``native_normals``: Philox2x32-10 (checked against the oracle's in
+    tests/test_policy_cpu.py) under native_key(mixed seed, block 2^31, step)
+    with the counter (lo32(gid), lo32(step) ^ hi32(gid) * 0x85EBCA77), gid =
+    env_offset * A + row, then Box-Muller in float64.
+
+    The bound of 1e-4 absolute is a discrimination threshold, not an accuracy
+    claim: the accuracy of v_sin_f32 / v_cos_f32 (angle in revolutions) on
+    this part has not been measured by anybody. A wrong word, key, counter or
+    row mapping, or swapped components, gives an unrelated normal, which lies
+    within 1e-4 in both components with probability about 3e-9 per row. What
+    the bound cannot see: a neighbouring point of the 24-bit grid (at most
+    2.2e-6 in z, below fp32's resolution here), and with it the convention at
+    the ends of u1's interval ((0, 1] against [0, 1)). The largest deviation
+    measured is printed and recorded in profiles/policy_parity.txt."""
+    P, A, O, H, seed, step, env_offset = NORMALS[name]
+    c, policy, obs, _ = on_device(pkg, (P, A, O, H), seed=seed, env_offset=env_offset)
+    eps_out = torch.empty(P * A, 2, device=DEV)
+    policy.act(obs, step_idx=step, eps_out=eps_out)
+    got = np_(eps_out).astype(np.float64)
+    want = pr.native_normals(seed, step, env_offset, P * A, A)
+    assert got.shape == want.shape and np.isfinite(got).all()
+    if env_offset:
+        assert env_offset * A < 2 ** 32 < (env_offset + P) * A      # crossed inside the batch
+    dev = np.abs(got - want)
+    row = int(dev.max(1).argmax())
+    text = (f"native normals vs the host restatement, {name} (P, A, O = {P}, {A}, {O}; seed {seed}, "
+            f"step {step}, env_offset {env_offset}): largest |eps_out - z64| {dev.max():.3e} at "
+            f"row {row} (z64 {want[row, 0]:+.6f}, {want[row, 1]:+.6f}), bound {NORMALS_BOUND:g}")
+    with capsys.disabled():
+        print("\n" + text)
+    out = os.environ.get("MARLNAV_POLICY_PARITY_OUT")
+    if out:
+        with open(out, "a") as fh:
+            fh.write(text + "\n")
+    assert dev.max() <= NORMALS_BOUND, text
 
 
 # ------------------------------------------------------------------------ collect

@@ -211,6 +211,97 @@ def test_held_tensors_keep_their_pre_call_values(pkg):
         assert_same(env.states, twin.states, "states")
 
 
+# ------------------------------------------------- the flag merge at any placement
+GUARD, FILL = 32, 0xA5      # guard bytes on either side of a flag region, and their fill
+
+
+def collect_with_flags_at(pkg, P, A, O, H, T, done_offset, trunc_offset):
+    """``collect_fused``'s call of marlnav_rollout_collect (rollout.py, from
+    ``env._sync_params()`` to ``env._engine.rollout(...)``) on a fresh env and
+    policy, with ``rollout.done`` and ``rollout.truncated`` taken at the given
+    byte offsets past a 16-byte boundary inside larger uint8 allocations
+    filled with FILL. -> (done region (T * P,), returns (T, P), the four guard
+    slices), as numpy arrays."""
+    abi = pkg.abi
+    env, policy = make_env(pkg, P, A, O), make_policy(pkg, A, O, H)
+    D = 2 + 2 * O + 2 * (A - 1)
+    n = T * P
+    buffer = pkg.RolloutBuffer(T)
+    env._sync_params()
+    if any(env._engine.shared_state()):
+        env._unshare_state(multi_step=True)
+    assert env._engine.fast_ok
+    lib = abi.load_library()
+    buffer.reserve(P, A, D, env.device)
+    r = abi.MarlnavRolloutBuffers()
+    for name, s in zip(abi.ROLLOUT_BUFFER_FIELDS, buffer._store):
+        setattr(r, name, s.data_ptr())
+    big = [torch.full((GUARD + 16 + n + GUARD,), FILL, dtype=torch.uint8, device=DEV)
+           for _ in range(2)]
+    regions = []
+    for t, off in zip(big, (done_offset, trunc_offset)):
+        assert t.data_ptr() % 16 == 0 and 0 <= off < 16
+        regions.append(t[GUARD + off:GUARD + off + n])
+        assert regions[-1].data_ptr() % 16 == off
+    r.done, r.truncated, r.eps = regions[0].data_ptr(), regions[1].data_ptr(), None
+    returns = torch.empty(T, P, dtype=torch.float64, device=DEV)
+    stats = torch.empty(2, dtype=torch.float64, device=DEV)
+    work = torch.empty(int(lib.marlnav_returns_work_size(P)), dtype=torch.float64, device=DEV)
+    raw, last = env._new_obs(), env._new_obs()
+    r.returns, r.returns_stats, r.returns_work = returns.data_ptr(), stats.data_ptr(), work.data_ptr()
+    pd, pb = policy._dims, policy._bufs
+    for f, t in policy._params:
+        setattr(pb, f, t.data_ptr())
+    pd.num_parallel = P
+    env._engine.rollout(abi.fn_addr(lib.marlnav_rollout_collect), bytes(pd), bytes(pb), bytes(r),
+                        raw.data_ptr(), last.data_ptr(), T, policy.seed, policy.step_idx,
+                        float(GAMMA))
+    torch.cuda.synchronize()
+    guards = []
+    for t, off in zip(big, (done_offset, trunc_offset)):
+        guards += [np_(t[:GUARD + off]), np_(t[GUARD + off + n:])]
+    return np_(regions[0]), np_(returns), guards
+
+
+_aligned_flags = {}
+
+
+def aligned_flags(pkg, T):
+    """The run with both flag stacks on a 16-byte boundary, once per T."""
+    if T not in _aligned_flags:
+        _aligned_flags[T] = collect_with_flags_at(pkg, 67, 3, 3, 50, T, 0, 0)
+    return _aligned_flags[T]
+
+
+@pytest.mark.parametrize("done_offset,trunc_offset,T", [
+    (0, 0, 5),        # head 0: 20 vectors and 15 tail bytes
+    (1, 1, 5),        # head 15, vector body, tail
+    (15, 15, 5),      # head 1
+    (3, 3, 1),        # 67 bytes: head 13 + 3 vectors + tail 6
+    (0, 4, 5),        # unequal placement: every byte singly
+    (5, 0, 5)])
+def test_flag_merge_at_every_placement(pkg, done_offset, trunc_offset, T):
+    """merge_flags_kernel's head / vector / tail split and its all-bytes
+    fallback are chosen from where ``done`` and ``truncated`` lie within 16
+    bytes; Python's fresh allocations only ever give head 0, the C ABI takes
+    any pointer. 67 x 3 x 3, 67 T flag bytes."""
+    P, A, O, H = 67, 3, 3, 50
+    want_done, want_returns, _ = aligned_flags(pkg, T)
+    via_buffer = pkg.RolloutBuffer(T)
+    pkg.collect_fused(make_env(pkg, P, A, O), make_policy(pkg, A, O, H), via_buffer, gamma=GAMMA)
+    np.testing.assert_array_equal(want_done, np_(via_buffer.stacked(5).view(torch.uint8)).ravel(),
+                                  "the helper's aligned run is collect_fused's")
+    done, returns, guards = collect_with_flags_at(pkg, P, A, O, H, T, done_offset, trunc_offset)
+    assert done.shape == (T * P,) and set(np.unique(done)) == {0, 1}, \
+        "done must hold both values, and only 0 and 1"
+    np.testing.assert_array_equal(done, want_done, "done")
+    for g, what in zip(guards, ("before done", "after done", "before truncated",
+                                "after truncated")):
+        assert g.size >= GUARD and (g == FILL).all(), f"guard bytes {what} were written"
+    assert returns.dtype == np.float64 and np.isfinite(returns).all()
+    np.testing.assert_array_equal(returns, want_returns, "returns")
+
+
 # ------------------------------------------------------------------- refusals
 def untouched(env, policy):
     return env._engine.steps_done == 0 and env._step_idx == 1 and policy.step_idx == 0
