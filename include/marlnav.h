@@ -536,6 +536,59 @@ int marlnav_ppo_critic_update(const MarlnavPpoDims *dims, const MarlnavPpoBuffer
                               double epsilon, const MarlnavAdamDims *adam_dims,
                               const MarlnavAdamBuffers *adam_bufs, void *stream);
 
+/* One whole MAPPO.train_actor / train_critic (models.py:160-198) in one call:
+ * num_epochs x num_batches minibatch updates enqueued back to back on
+ * `stream`, epoch-major, with no synchronisation and no allocation.
+ *   network     MARLNAV_NETWORK_ACTOR or MARLNAV_NETWORK_CRITIC
+ *   dims        P, A, D, H of the rollout buffer; num_steps = its stored steps
+ *   bufs        as for marlnav_ppo_*_update, the data pointers addressing
+ *               step 0 of the stacked storage; `loss` is not used; `work` has
+ *               marlnav_ppo_train_work_size(dims, bounds, num_batches) doubles
+ *   bounds      host array of num_batches (lo, hi) pairs: minibatch j is
+ *               steps lo..hi-1, 0 <= lo < hi <= num_steps
+ *   adam        the network's own table, checked as marlnav_ppo_*_update does
+ *   loss_log    device, num_epochs * num_batches doubles: update k (epoch e,
+ *               batch j: k = e * num_batches + j) writes its loss to [k]
+ * Update k stores what marlnav_ppo_*_update on steps lo..hi stores, bit for
+ * bit: loss, every .grad, parameters, both moments, the step count. Where it
+ * was measured to be faster (an actor of up to 1024 elements, a critic
+ * minibatch of up to 2^17 env rows) it takes fewer launches: one thread of the
+ * gradient pass advances the count and publishes the step's scalars, and the
+ * finish launch, which follows in stream order, applies the Adam element
+ * update to each element as it stores its gradient (2 launches for the actor,
+ * 2-3 for the critic); elsewhere it enqueues the launches of
+ * marlnav_ppo_*_update. ent_const is ignored for the critic. Everything is
+ * validated before the first launch (MARLNAV_EINVAL, the message names the
+ * field). */
+#define MARLNAV_NETWORK_ACTOR 0
+#define MARLNAV_NETWORK_CRITIC 1
+int marlnav_ppo_train_phase(int network, const MarlnavPpoDims *dims,
+                            const MarlnavPpoBuffers *bufs, const int64_t *bounds,
+                            int64_t num_batches, int64_t num_epochs, double epsilon,
+                            double ent_const, const MarlnavAdamDims *adam_dims,
+                            const MarlnavAdamBuffers *adam_bufs, double *loss_log, void *stream);
+
+/* fp64 elements of `work` that cover the largest minibatch of the list;
+ * negative on bad dims or bounds. */
+int64_t marlnav_ppo_train_work_size(const MarlnavPpoDims *dims, const int64_t *bounds,
+                                    int64_t num_batches);
+
+/* The checkpoint rule of MAPPO.get_data (models.py:127-129) on the device: if
+ * *mean_rew > *max_rew (fp64; a NaN mean is not greater), copy src[i] to
+ * dst[i] (numel[i] fp32 elements, any 4-byte alignment, i < num_tensors <=
+ * MARLNAV_SNAPSHOT_MAX_TENSORS), add 1 to save_state[0], set save_state[1] =
+ * repeat_index and, with track_best = 1, *max_rew = *mean_rew. The reference
+ * never updates its maximum (track_best = 0: every rollout with a non-NaN
+ * mean saves). src, dst, numel are host arrays; mean_rew, max_rew and
+ * save_state (2 int64) are device pointers, 8-byte aligned. Two launches: the
+ * copy, then one bookkeeping thread, so no block reads a decision written in
+ * its own launch. */
+#define MARLNAV_SNAPSHOT_MAX_TENSORS 10
+int marlnav_params_snapshot_if(int num_tensors, const float *const *src, float *const *dst,
+                               const int64_t *numel, const double *mean_rew, double *max_rew,
+                               int64_t *save_state, int64_t repeat_index, int track_best,
+                               void *stream);
+
 /* Testing hook (not part of the reference's interface): restrict the step /
  * observe kernel selection to one family, process-wide. 0 = automatic (the
  * default); a family that does not support the call's shape or buffer

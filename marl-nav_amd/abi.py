@@ -164,6 +164,9 @@ class MarlnavAdamBuffers(ctypes.Structure):
                 + [("state", _P)])
 
 
+NETWORK_ACTOR, NETWORK_CRITIC = 0, 1
+SNAPSHOT_MAX_TENSORS = 10
+
 EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_formation_obs",
            "marlnav_counter_slots", "marlnav_counters_total",
            "marlnav_returns_work_size", "marlnav_discounted_returns", "marlnav_policy_act",
@@ -171,6 +174,8 @@ EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_for
            "marlnav_ppo_work_size", "marlnav_ppo_actor_grad", "marlnav_ppo_critic_grad",
            "marlnav_adam_state_size", "marlnav_adam_step",
            "marlnav_ppo_actor_update", "marlnav_ppo_critic_update",
+           "marlnav_ppo_train_phase", "marlnav_ppo_train_work_size",
+           "marlnav_params_snapshot_if",
            "marlnav_last_error", "marlnav_abi_version",
            "marlnav_debug_force_family", "marlnav_debug_last_family",
            "marlnav_debug_acos_range", "marlnav_debug_fastdiv_check")
@@ -238,6 +243,16 @@ def _declare(lib):
     lib.marlnav_ppo_critic_update.argtypes = [ppo_dims_p, ppo_bufs_p, c.c_double,
                                               adam_dims_p, adam_bufs_p, _P]
     lib.marlnav_ppo_critic_update.restype = c.c_int
+    i64_p = c.POINTER(c.c_int64)
+    lib.marlnav_ppo_train_phase.argtypes = [c.c_int, ppo_dims_p, ppo_bufs_p, i64_p, c.c_int64,
+                                            c.c_int64, c.c_double, c.c_double, adam_dims_p,
+                                            adam_bufs_p, _P, _P]
+    lib.marlnav_ppo_train_phase.restype = c.c_int
+    lib.marlnav_ppo_train_work_size.argtypes = [ppo_dims_p, i64_p, c.c_int64]
+    lib.marlnav_ppo_train_work_size.restype = c.c_int64
+    lib.marlnav_params_snapshot_if.argtypes = [c.c_int, c.POINTER(_P), c.POINTER(_P), i64_p, _P, _P,
+                                               _P, c.c_int64, c.c_int, _P]
+    lib.marlnav_params_snapshot_if.restype = c.c_int
     lib.marlnav_last_error.argtypes = []
     lib.marlnav_last_error.restype = c.c_char_p
     lib.marlnav_abi_version.argtypes = []

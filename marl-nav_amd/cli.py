@@ -2,9 +2,10 @@
 ``python -m marlnav`` (marlnav/__main__.py): same arguments and defaults.
 
 Implemented modes: the reward check (``-rc``, utils.py:579-666 via
-__main__.py:36-42) on the HIP environment step. Training (MAPPO) and
-rendering are the reference's own code and stay there: they take
-``marlnav_amd.Env`` as their environment.
+__main__.py:36-42) on the HIP environment step, and the two marlnav_amd-only
+flags below. Without a mode flag (the reference's training default) and with
+``-re`` the command says what to use and returns 2: the reference's own MAPPO
+and animation take ``marlnav_amd.Env`` as their environment.
 
     python -m marlnav_amd -rc -se 0            # config-1 reward check
     python -m marlnav_amd -rc -sn 0 -ms 400    # mock scenario 0
@@ -15,6 +16,13 @@ per frame in the reference (animation.py:40-71), without the window, and
 prints the episode figures as one JSON line.
 
     python -m marlnav_amd --evaluate -w weights/X_actor.pt -np 4096 -ms 1000
+
+``--train`` (marlnav_amd only) is the reference's default mode (__main__.py:
+16-28) on the device (``marlnav_amd.MAPPO``): ``num_total // (buffer_len *
+num_parallel)`` repeats of rollout, actor phase and critic phase, then the
+reference's weight files, CSVs, params file and figures, and one JSON line.
+
+    python -m marlnav_amd --train -np 4096 -bl 16 -bs 8 -ne 4 -nt 1048576
 """
 import argparse
 import sys
@@ -78,6 +86,17 @@ def build_parser():
     a('--trace-out', metavar='FILE.npz',
       help='with --evaluate: save the traced env\'s states, obstacles, target, rewards and '
            'flags of every step')
+    a('--train', action='store_true',
+      help='train on the device with the model arguments above (-hs -lr -ec -ep -g -nt -bl '
+           '-ne -bs) and write weights/, logs/ and plots/ under --out-dir; prints one JSON '
+           'line')
+    a('--track-best', action='store_true',
+      help='with --train: keep the weights of the rollout with the highest mean reward (the '
+           'reference never raises its maximum and so keeps the weights from before the '
+           'last repeat\'s training, which is the default here too)')
+    a('--save-every', type=int, default=0, metavar='N',
+      help='with --train: also write the weight files after every N repeats')
+    a('--out-dir', default='.', help='with --train: where weights/, logs/ and plots/ go')
     a('--plot-dir', default='plots', help='directory of the saved figures')
     a('--no-plots', action='store_true', help='skip the figures, print the series')
     return p
@@ -91,12 +110,15 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.evaluate:
         return _evaluate(pkg, args)
+    if args.train:
+        return _train(pkg, args)
     if not args.reward_check:
         mode = 'rendering' if args.rendering else 'training'
         print(f"marlnav_amd implements the environment step; {mode} is the reference's "
               "own code (MAPPO / animation): run it with marlnav_amd.Env as its "
               "environment (INTEGRATION.md). Use -rc for the reward check, --evaluate to run "
-              "a trained actor without the window.",
+              "a trained actor without the window, --train for the device training mode "
+              "(marlnav_amd.MAPPO).",
               file=sys.stderr)
         return 2
     if not torch.cuda.is_available():
@@ -160,6 +182,42 @@ def _evaluate(pkg, args):
         np.savez(args.trace_out, **trace)
     if not args.no_plots:
         _plot_trace(trace, args)
+    return 0
+
+
+def _train(pkg, args):
+    """``--train``: main()'s training branch (__main__.py:16-28)."""
+    import json
+
+    import torch
+    if not torch.cuda.is_available():
+        print("marlnav_amd needs a HIP device (no CPU fallback)", file=sys.stderr)
+        return 1
+    device = 'cuda'
+    if args.seed is not None:
+        pkg.set_all_seeds(args.seed)
+    try:
+        model_params = pkg.set_model_params(args, device)
+    except ValueError as e:
+        print(f"--train: {e}", file=sys.stderr)
+        return 2
+    env_params = pkg.set_env_params(args, device)
+    env_params['rng'] = 'native'           # the host is not in the loop: in-kernel re-init
+    if args.seed is not None:
+        env_params['seed'] = args.seed
+    env = pkg.Env(env_params)
+    mappo = pkg.MAPPO(model_params, env, seed=args.seed or 0, track_best=args.track_best,
+                      out_dir=args.out_dir)
+    repeats = args.num_total // (args.buffer_len * args.num_parallel)
+    weights = mappo.run(repeats, save_every=args.save_every or None)
+    full = {'env': env_params, 'model': model_params,
+            'animation': pkg.utils.set_animation_params(args, device)}
+    files = mappo.save_stats(full, plot=not args.no_plots)
+    logs = mappo._logs
+    print(json.dumps({"repeats": repeats,
+                      "last_mean_rew": logs['mean_rews'][-1] if logs['mean_rews'] else None,
+                      "saves": mappo.save_count()[0],
+                      "weights": list(weights) if weights else [], "files": files}))
     return 0
 
 

@@ -23,6 +23,13 @@
 // (rounded) m and v, so a run continued from a checkpoint repeats the run
 // that was not interrupted. No atomics, no reduction: equal inputs give equal
 // bits. Built with -ffp-contract=off: the FMAs below are explicit.
+//
+// Also here, for the training mode: marlnav_ppo_train_phase,
+// a whole train_actor / train_critic enqueued by one call, whose updates hand
+// the Adam step to marlnav_ppo.hip's finish kernels (adam_element.h is the
+// shared element update) where that is faster and enqueue the two launches
+// above elsewhere; and marlnav_params_snapshot_if, the reference's checkpoint
+// rule as a copy launch and one bookkeeping thread.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -30,6 +37,7 @@
 #include <stdio.h>
 
 #include "../../include/marlnav.h"
+#include "adam_element.h"
 
 __attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const char *msg);
 
@@ -39,13 +47,9 @@ constexpr int kThreads = 256;
 constexpr int kSlots = MARLNAV_ADAM_MAX_TENSORS;
 constexpr int64_t kMaxElements = (int64_t)1 << 40;  // all slots together
 
-// MarlnavAdamBuffers.state
-struct AdamState {
-    int64_t step;      // steps taken
-    double step_size;  // lr / (1 - beta1^step)
-    double bc2_sqrt;   // sqrt(1 - beta2^step)
-    double reserved;
-};
+using marlnav_adam::AdamScalars;
+using marlnav_adam::AdamState;
+using marlnav_adam::adam_element;
 
 struct AdamArgs {
     float *param[kSlots];
@@ -64,27 +68,7 @@ __global__ void __launch_bounds__(64) adam_advance(AdamState *s, double lr, doub
                                                     double beta2)
 {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const int64_t k = s->step + 1;
-    s->step = k;
-    const double bc1 = 1.0 - pow(beta1, (double)k);
-    const double bc2 = 1.0 - pow(beta2, (double)k);
-    s->step_size = lr / bc1;
-    s->bc2_sqrt = sqrt(bc2);
-}
-
-struct AdamScalars {
-    double beta1, beta2, omb1, omb2, eps, step_size, bc2_sqrt;
-    bool maximize;
-};
-
-__device__ __forceinline__ void adam_element(float &p, float g, float &m, float &v,
-                                             const AdamScalars &c)
-{
-    const double gd = c.maximize ? -(double)g : (double)g;
-    m = (float)__builtin_fma(c.beta1, (double)m, c.omb1 * gd);
-    v = (float)__builtin_fma(c.beta2, (double)v, (c.omb2 * gd) * gd);
-    const double denom = sqrt((double)v) / c.bc2_sqrt + c.eps;
-    p = (float)((double)p - c.step_size * ((double)m / denom));
+    marlnav_adam::adam_advance_one(s, lr, beta1, beta2);
 }
 
 __global__ void __launch_bounds__(kThreads) adam_apply(AdamArgs a)
@@ -335,4 +319,265 @@ extern "C" int marlnav_ppo_critic_update(const MarlnavPpoDims *d, const MarlnavP
     rc = marlnav_ppo_critic_grad(d, b, epsilon, stream);
     if (rc) return rc;
     return enqueue_adam(ad, ab, (hipStream_t)stream);
+}
+
+// =========================================================================
+// one whole train_actor / train_critic as one call
+// =========================================================================
+__attribute__((visibility("hidden"))) int marlnav_internal_ppo_fold(
+    int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
+    double ent_const, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, void *stream,
+    int check_only);
+
+namespace {
+
+int fail_ll(const char *fmt, long long a, long long b, long long c)
+{
+    char msg[256];
+    snprintf(msg, sizeof(msg), fmt, a, b, c);
+    return marlnav_internal_fail(MARLNAV_EINVAL, msg);
+}
+
+// the (lo, hi) list against the buffer's steps
+int check_bounds(const MarlnavPpoDims *d, const int64_t *bounds, int64_t num_batches)
+{
+    if (num_batches < 1)
+        return fail_ll("train: num_batches=%lld < 1", num_batches, 0, 0);
+    if (!bounds) return marlnav_internal_fail(MARLNAV_EINVAL, "train: bounds is NULL");
+    for (int64_t j = 0; j < num_batches; ++j) {
+        const int64_t lo = bounds[2 * j], hi = bounds[2 * j + 1];
+        if (lo < 0 || hi <= lo || hi > d->num_steps) {
+            char msg[256];
+            snprintf(msg, sizeof(msg),
+                     "train: bounds[%lld]=(%lld, %lld) is not a non-empty range of the %lld steps",
+                     (long long)j, (long long)lo, (long long)hi, (long long)d->num_steps);
+            return marlnav_internal_fail(MARLNAV_EINVAL, msg);
+        }
+    }
+    return 0;
+}
+
+// the structs of minibatch (lo, hi): dims of hi - lo steps, data pointers at step lo
+void minibatch(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, int64_t lo, int64_t hi,
+               double *loss, MarlnavPpoDims *md, MarlnavPpoBuffers *mb)
+{
+    *md = *d;
+    md->num_steps = hi - lo;
+    *mb = *b;
+    const int64_t rows = lo * d->num_parallel, arows = rows * d->num_agents;
+    mb->obs = b->obs + arows * d->obs_dim;
+    if (b->actions) mb->actions = b->actions + arows * 2;
+    if (b->log_probs) mb->log_probs = b->log_probs + arows;
+    mb->values = b->values + rows;
+    mb->returns = b->returns + rows;
+    mb->loss = loss;
+}
+
+}  // namespace
+
+extern "C" int64_t marlnav_ppo_train_work_size(const MarlnavPpoDims *d, const int64_t *bounds,
+                                               int64_t num_batches)
+{
+    if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
+    const int rc = check_bounds(d, bounds, num_batches);
+    if (rc) return rc;
+    int64_t need = 0;
+    for (int64_t j = 0; j < num_batches; ++j) {
+        MarlnavPpoDims md = *d;
+        md.num_steps = bounds[2 * j + 1] - bounds[2 * j];
+        const int64_t w = marlnav_ppo_work_size(&md);
+        if (w < 0) return w;
+        if (w > need) need = w;
+    }
+    return need;
+}
+
+extern "C" int marlnav_ppo_train_phase(int network, const MarlnavPpoDims *d,
+                                       const MarlnavPpoBuffers *b, const int64_t *bounds,
+                                       int64_t num_batches, int64_t num_epochs, double epsilon,
+                                       double ent_const, const MarlnavAdamDims *ad,
+                                       const MarlnavAdamBuffers *ab, double *loss_log,
+                                       void *stream)
+{
+    // ---- every check before the first launch
+    if (network != MARLNAV_NETWORK_ACTOR && network != MARLNAV_NETWORK_CRITIC)
+        return fail_ll("train: network=%lld must be MARLNAV_NETWORK_ACTOR or _CRITIC", network, 0,
+                       0);
+    if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
+    if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
+    if (num_epochs < 1) return fail_ll("train: num_epochs=%lld < 1", num_epochs, 0, 0);
+    int rc = check_bounds(d, bounds, num_batches);
+    if (rc) return rc;
+    if (!loss_log) return marlnav_internal_fail(MARLNAV_EINVAL, "train: loss_log is NULL");
+    if (addr(loss_log) & 7u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "train: loss_log must be 8-byte aligned");
+    rc = check_adam(ad, ab);
+    if (rc) return rc;
+    const int64_t H = d->hidden_size, D = d->obs_dim, AD = (int64_t)d->num_agents * D;
+    if (network == MARLNAV_NETWORK_ACTOR) {
+        const float *const w[6] = {b->actor_fc1_w, b->actor_fc1_b, b->actor_mu_w,
+                                   b->actor_mu_b,  b->actor_std_w, b->actor_std_b};
+        float *const gw[6] = {b->grad_actor_fc1_w, b->grad_actor_fc1_b, b->grad_actor_mu_w,
+                              b->grad_actor_mu_b,  b->grad_actor_std_w, b->grad_actor_std_b};
+        const int64_t size[6] = {H * D, H, 2 * H, 2, 2 * H, 2};
+        const char *const name[6] = {"actor_fc1_w", "actor_fc1_b", "actor_mu_w",
+                                     "actor_mu_b",  "actor_std_w", "actor_std_b"};
+        rc = check_table("actor", 6, w, gw, size, name, ad, ab);
+    } else {
+        const float *const w[4] = {b->critic_fc1_w, b->critic_fc1_b, b->critic_fc2_w,
+                                   b->critic_fc2_b};
+        float *const gw[4] = {b->grad_critic_fc1_w, b->grad_critic_fc1_b, b->grad_critic_fc2_w,
+                              b->grad_critic_fc2_b};
+        const int64_t size[4] = {H * AD, H, H, 1};
+        const char *const name[4] = {"critic_fc1_w", "critic_fc1_b", "critic_fc2_w",
+                                     "critic_fc2_b"};
+        rc = check_table("critic", 4, w, gw, size, name, ad, ab);
+    }
+    if (rc) return rc;
+    if (!b->obs) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer obs is NULL");
+    if (!b->values) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer values is NULL");
+    if (!b->returns) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer returns is NULL");
+    MarlnavPpoDims md;
+    MarlnavPpoBuffers mb;
+    for (int64_t j = 0; j < num_batches; ++j) {  // dims and buffers of every minibatch
+        minibatch(d, b, bounds[2 * j], bounds[2 * j + 1], loss_log, &md, &mb);
+        rc = marlnav_internal_ppo_fold(network, &md, &mb, epsilon, ent_const, ad, ab, stream, 1);
+        if (rc) return rc;
+    }
+    // ---- num_epochs x num_batches updates, epoch-major: two launches for the
+    // actor, two or three for the critic, each with the Adam step inside (a
+    // large actor keeps the four launches of marlnav_ppo_actor_update)
+    int64_t k = 0;
+    for (int64_t e = 0; e < num_epochs; ++e)
+        for (int64_t j = 0; j < num_batches; ++j, ++k) {
+            minibatch(d, b, bounds[2 * j], bounds[2 * j + 1], loss_log + k, &md, &mb);
+            rc = marlnav_internal_ppo_fold(network, &md, &mb, epsilon, ent_const, ad, ab, stream,
+                                           0);
+            if (rc == 1) rc = enqueue_adam(ad, ab, (hipStream_t)stream);  // not folded
+            if (rc) return rc;
+        }
+    return 0;
+}
+
+// =========================================================================
+// the checkpoint rule of MAPPO.get_data on the device (models.py:127-129)
+// =========================================================================
+namespace {
+
+constexpr int kSnapSlots = MARLNAV_SNAPSHOT_MAX_TENSORS;
+
+struct SnapArgs {
+    const float *src[kSnapSlots];
+    float *dst[kSnapSlots];
+    int64_t numel[kSnapSlots];
+    int64_t item_end[kSnapSlots];  // items of slots 0..i; unused slots repeat the total
+    const double *mean_rew;
+    const double *max_rew;
+    uint32_t vec_mask;  // bit i: both pointers of slot i are 16-byte aligned
+};
+
+// thread = item of 4 elements over all slots, as adam_apply; every thread
+// reads the decision, which no thread of this launch writes
+__global__ void __launch_bounds__(kThreads) snapshot_copy(SnapArgs a)
+{
+    const int64_t item = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (item >= a.item_end[kSnapSlots - 1]) return;
+    if (!(*a.mean_rew > *a.max_rew)) return;  // a NaN mean copies nothing
+    const float *src = a.src[0];
+    float *dst = a.dst[0];
+    int64_t n = a.numel[0], first = 0;
+    bool vec = a.vec_mask & 1u;
+#pragma unroll
+    for (int i = 1; i < kSnapSlots; ++i)
+        if (item >= a.item_end[i - 1]) {  // never true for an unused slot
+            src = a.src[i];
+            dst = a.dst[i];
+            n = a.numel[i];
+            first = a.item_end[i - 1];
+            vec = (a.vec_mask >> i) & 1u;
+        }
+    const int64_t e0 = (item - first) * 4;  // < n: a slot has ceil(n / 4) items
+    const int64_t left = n - e0;
+    if (vec && left >= 4) {
+        *reinterpret_cast<float4 *>(dst + e0) = *reinterpret_cast<const float4 *>(src + e0);
+    } else {
+        const int cnt = left < 4 ? (int)left : 4;
+        for (int j = 0; j < cnt; ++j) dst[e0 + j] = src[e0 + j];
+    }
+}
+
+// one thread, the launch after the copy: the save count, the repeat index of
+// the save and, with track_best, the new maximum
+__global__ void __launch_bounds__(64) snapshot_book(const double *mean_rew, double *max_rew,
+                                                     int64_t *save_state, int64_t repeat_index,
+                                                     int track_best)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const double mean = *mean_rew;
+    if (!(mean > *max_rew)) return;
+    save_state[0] += 1;
+    save_state[1] = repeat_index;
+    if (track_best) *max_rew = mean;
+}
+
+}  // namespace
+
+extern "C" int marlnav_params_snapshot_if(int num_tensors, const float *const *src,
+                                          float *const *dst, const int64_t *numel,
+                                          const double *mean_rew, double *max_rew,
+                                          int64_t *save_state, int64_t repeat_index,
+                                          int track_best, void *stream)
+{
+    if (num_tensors < 1 || num_tensors > kSnapSlots)
+        return fail_slot("snapshot: num_tensors=%d outside [1, %lld]", num_tensors, kSnapSlots);
+    if (!src) return marlnav_internal_fail(MARLNAV_EINVAL, "snapshot: src is NULL");
+    if (!dst) return marlnav_internal_fail(MARLNAV_EINVAL, "snapshot: dst is NULL");
+    if (!numel) return marlnav_internal_fail(MARLNAV_EINVAL, "snapshot: numel is NULL");
+    int64_t total = 0;
+    for (int i = 0; i < num_tensors; ++i) {
+        if (numel[i] < 1) return fail_slot("snapshot: numel[%d]=%lld < 1", i, numel[i]);
+        if (numel[i] > kMaxElements - total)
+            return fail_slot("snapshot: numel[%d]=%lld brings the table past 2^40 elements", i,
+                             numel[i]);
+        total += numel[i];
+        if (!src[i]) return fail_slot("snapshot: src[%d] is NULL", i, 0);
+        if (!dst[i]) return fail_slot("snapshot: dst[%d] is NULL", i, 0);
+        if (addr(src[i]) & 3u) return fail_slot("snapshot: src[%d] must be 4-byte aligned", i, 0);
+        if (addr(dst[i]) & 3u) return fail_slot("snapshot: dst[%d] must be 4-byte aligned", i, 0);
+    }
+    if (!mean_rew) return marlnav_internal_fail(MARLNAV_EINVAL, "snapshot: mean_rew is NULL");
+    if (!max_rew) return marlnav_internal_fail(MARLNAV_EINVAL, "snapshot: max_rew is NULL");
+    if (!save_state) return marlnav_internal_fail(MARLNAV_EINVAL, "snapshot: save_state is NULL");
+    if ((addr(mean_rew) | addr(max_rew) | addr(save_state)) & 7u)
+        return marlnav_internal_fail(
+            MARLNAV_EINVAL, "snapshot: mean_rew, max_rew and save_state must be 8-byte aligned");
+    if (repeat_index < 0)
+        return fail_ll("snapshot: repeat_index=%lld < 0", repeat_index, 0, 0);
+    if (track_best != 0 && track_best != 1)
+        return fail_slot("snapshot: track_best=%d must be 0 or 1", track_best, 0);
+
+    SnapArgs a;
+    int64_t items = 0;
+    a.vec_mask = 0;
+    for (int i = 0; i < kSnapSlots; ++i) {
+        const bool used = i < num_tensors;
+        a.src[i] = used ? src[i] : nullptr;
+        a.dst[i] = used ? dst[i] : nullptr;
+        a.numel[i] = used ? numel[i] : 0;
+        if (used) {
+            items += (numel[i] + 3) / 4;
+            if (((addr(src[i]) | addr(dst[i])) & 15u) == 0) a.vec_mask |= 1u << i;
+        }
+        a.item_end[i] = items;
+    }
+    a.mean_rew = mean_rew;
+    a.max_rew = max_rew;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(snapshot_copy, dim3((unsigned)((items + kThreads - 1) / kThreads)),
+                       dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(snapshot_book, dim3(1), dim3(64), 0, s, mean_rew, max_rew, save_state,
+                       repeat_index, track_best);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
+    return 0;
 }

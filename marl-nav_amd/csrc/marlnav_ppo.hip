@@ -37,6 +37,12 @@
 // workspace instead of being recomputed per tile. critic_finish adds the
 // chunk partials per output element in chunk order.
 //
+// The kernels take a trailing argument pack. Empty, they are the kernels of
+// marlnav_ppo_*_grad. With AdvArgs a pass kernel's last act is one thread
+// advancing Adam's step count; with FoldArgs a finish kernel applies the Adam
+// element update to every gradient element it has stored (the training
+// phase call of marlnav_adam.hip).
+//
 // Determinism: no atomics, every sum in a fixed order that depends on the
 // dims only. Built with -ffp-contract=off: every FMA below is explicit.
 #include <hip/hip_runtime.h>
@@ -45,6 +51,7 @@
 #include <stdio.h>
 
 #include "../../include/marlnav.h"
+#include "adam_element.h"
 
 __attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const char *msg);
 
@@ -82,6 +89,63 @@ struct PpoArgs {
     double *fw_part;         // [fw_blocks][2 H + 2]: dbc, dW2, db2, loss sum
     float clip_lo, clip_hi, eps_f, ent_f;
 };
+
+// ---- the Adam step folded into the finish kernels (marlnav_ppo_train_phase,
+// DESIGN.md §14). AdvArgs: what one thread of the pass launch needs to advance
+// the count and publish the step's scalars. FoldArgs: what the finish launch,
+// which follows in stream order, needs to update every element it has just
+// written to .grad. Slots in the network's declaration order (the actor's six,
+// the critic's four).
+using marlnav_adam::AdamScalars;
+using marlnav_adam::AdamState;
+
+struct AdvArgs {
+    AdamState *state;
+    double lr, beta1, beta2;
+};
+
+struct FoldArgs {
+    float *param[6];
+    float *exp_avg[6];
+    float *exp_avg_sq[6];
+    const AdamState *state;
+    double beta1, beta2, omb1, omb2, eps;  // omb = 1 - beta
+    int maximize;
+};
+
+__device__ __forceinline__ AdamScalars fold_scalars(const FoldArgs &f)
+{
+    AdamScalars c;
+    c.beta1 = f.beta1;
+    c.beta2 = f.beta2;
+    c.omb1 = f.omb1;
+    c.omb2 = f.omb2;
+    c.eps = f.eps;
+    c.step_size = f.state->step_size;
+    c.bc2_sqrt = f.state->bc2_sqrt;
+    c.maximize = f.maximize != 0;
+    return c;
+}
+
+// element e of one slot, from the fp32 gradient this thread has stored
+__device__ __forceinline__ void fold_element(const FoldArgs &f, int slot, int64_t e, float grad,
+                                             const AdamScalars &c)
+{
+    float p = f.param[slot][e], m = f.exp_avg[slot][e], v = f.exp_avg_sq[slot][e];
+    marlnav_adam::adam_element(p, grad, m, v, c);
+    f.exp_avg[slot][e] = m;
+    f.exp_avg_sq[slot][e] = v;
+    f.param[slot][e] = p;
+}
+
+// The kernels below take the fold's arguments as a trailing pack: empty for
+// the launches of marlnav_ppo_*_grad / _update, whose instantiations are the
+// kernels as they were; one AdvArgs / FoldArgs for the folded ones.
+template <class T>
+__device__ __forceinline__ const T &only(const T &x)
+{
+    return x;
+}
 
 __device__ __forceinline__ float relu_t(float a) { return a < 0.0f ? 0.0f : a; }  // NaN stays
 
@@ -134,7 +198,8 @@ static_assert(actor_lds_bytes(kMaxD) <= 64 * 1024, "LDS of the widest row");
 // ones column), then the surrogate sum and the entropy sum
 __device__ __host__ inline int64_t actor_stride(int D) { return 4 * (int64_t)(D + 1) + 2; }
 
-__global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g)
+template <class... X>
+__global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
 {
     const int D = g.D, H = g.H;
     const int ncol = D + 1;
@@ -309,11 +374,26 @@ __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g)
         out[4 * ncol] = bs;
         out[4 * ncol + 1] = bent;
     }
+    if constexpr (sizeof...(X) != 0) {
+        // the count of the update this launch belongs to: one thread, read by
+        // no thread of this launch, by every thread of the finish launch. Last
+        // in the kernel, where nothing else is live: its pow() at the start
+        // raised the critic pass from 88 to 111 VGPRs
+        const AdvArgs &adv = only(x...);
+        if (blockIdx.x == 0 && t == 0)
+            marlnav_adam::adam_advance_one(adv.state, adv.lr, adv.beta1, adv.beta2);
+    }
 }
 
 // one block: S and the loss sums added over the blocks in block order, then
 // the epilogue. LDS: 4 (D + 1) + 2 doubles of totals, group partials before.
-__global__ void __launch_bounds__(kThreads) actor_finish(PpoArgs g)
+//
+// ADAM: every thread then runs the Adam element update of the elements it has
+// stored, from the stored fp32 values. The block barrier between the two
+// halves puts every read of a parameter (the epilogue reads W1, b1 and the
+// heads) before the first write of one.
+template <class... X>
+__global__ void __launch_bounds__(kThreads) actor_finish(PpoArgs g, X... x)
 {
     const int D = g.D, H = g.H, ncol = D + 1;
     const int nS = 4 * ncol + 2;
@@ -372,7 +452,32 @@ __global__ void __launch_bounds__(kThreads) actor_finish(PpoArgs g)
         else
             g.b.grad_actor_fc1_b[j] = (float)a;
     }
+    if constexpr (sizeof...(X) != 0) {
+        __syncthreads();
+        const FoldArgs &f = only(x...);
+        const AdamScalars c = fold_scalars(f);
+        // the same thread -> element maps as above; slots: fc1_w, fc1_b, mu_w,
+        // mu_b, std_w, std_b
+        for (int idx = t; idx < 4 * H; idx += kThreads) {
+            const int r = idx / H, j = idx - r * H;
+            const int64_t e = (r & 1) * H + j;
+            fold_element(f, r < 2 ? 2 : 4, e,
+                         (r < 2 ? g.b.grad_actor_mu_w : g.b.grad_actor_std_w)[e], c);
+        }
+        if (t < 4)
+            fold_element(f, t < 2 ? 3 : 5, t & 1,
+                         (t < 2 ? g.b.grad_actor_mu_b : g.b.grad_actor_std_b)[t & 1], c);
+        for (int64_t idx = t; idx < (int64_t)H * ncol; idx += kThreads) {
+            const int j = (int)(idx / ncol), cc = (int)(idx - (int64_t)j * ncol);
+            if (cc < D)
+                fold_element(f, 0, (int64_t)j * D + cc, g.b.grad_actor_fc1_w[(int64_t)j * D + cc],
+                             c);
+            else
+                fold_element(f, 1, j, g.b.grad_actor_fc1_b[j], c);
+        }
+    }
 }
+
 
 // =========================================================================
 // critic
@@ -423,9 +528,9 @@ constexpr size_t kCriticLdsBytes =
 // MODE kBackward: the outer product alone, dh read back from the workspace.
 enum { kFused = 0, kForward = 1, kBackward = 2 };
 
-template <int JT, int MODE>
+template <int JT, int MODE, class... X>
 __global__ void __launch_bounds__(kThreads) critic_pass(PpoArgs g, CriticTiling ct, float *dhbuf,
-                                                         int hp, int vec4)
+                                                         int hp, int vec4, X... x)
 {
     const int A = g.A, D = g.D, H = g.H;
     const int AD = A * D;
@@ -647,10 +752,19 @@ __global__ void __launch_bounds__(kThreads) critic_pass(PpoArgs g, CriticTiling 
             vout[2 * H + 1] = sl;
         }
     }
+    if constexpr (sizeof...(X) != 0) {
+        // as in actor_pass: the first launch of the update advances the count
+        const AdvArgs &adv = only(x...);
+        if (blockIdx.x == 0 && blockIdx.y == 0 && t == 0)
+            marlnav_adam::adam_advance_one(adv.state, adv.lr, adv.beta1, adv.beta2);
+    }
 }
 
-// thread = output element: its chunk partials added in chunk order
-__global__ void __launch_bounds__(kThreads) critic_finish(PpoArgs g)
+// thread = output element: its chunk partials added in chunk order. ADAM: the
+// thread then updates that element of the parameter (critic_finish reads no
+// parameter, so no thread of the launch reads what another writes).
+template <class... X>
+__global__ void __launch_bounds__(kThreads) critic_finish(PpoArgs g, X... x)
 {
     const int H = g.H, AD = g.A * g.D;
     const int64_t stride = critic_stride(AD, H);
@@ -673,7 +787,22 @@ __global__ void __launch_bounds__(kThreads) critic_finish(PpoArgs g)
         g.b.grad_critic_fc2_b[0] = (float)a;
     else
         g.b.loss[0] = a / (double)g.N;
+    if constexpr (sizeof...(X) != 0) {
+        if (idx > nW + 2 * H) return;  // the loss
+        const FoldArgs &f = only(x...);
+        const AdamScalars c = fold_scalars(f);
+        const float gf = (float)a;     // the value stored above
+        if (idx < nW)
+            fold_element(f, 0, idx, gf, c);
+        else if (idx < nW + H)
+            fold_element(f, 1, idx - nW, gf, c);
+        else if (idx < nW + 2 * H)
+            fold_element(f, 2, idx - nW - H, gf, c);
+        else
+            fold_element(f, 3, 0, gf, c);
+    }
 }
+
 
 // ---- host side
 int failf(int code, const char *fmt, long long a, long long b, long long c)
@@ -800,11 +929,10 @@ extern "C" int64_t marlnav_ppo_work_size(const MarlnavPpoDims *d)
     return actor > critic ? actor : critic;
 }
 
-extern "C" int marlnav_ppo_actor_grad(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
-                                      double epsilon, double ent_const, void *stream)
+namespace {
+
+int check_actor_bufs(const MarlnavPpoBuffers *b)
 {
-    const int rc = check_dims(d);
-    if (rc) return rc;
     if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
     PPO_NEED(obs);
     PPO_NEED(actions);
@@ -825,31 +953,11 @@ extern "C" int marlnav_ppo_actor_grad(const MarlnavPpoDims *d, const MarlnavPpoB
     PPO_NEED(grad_actor_std_b);
     PPO_NEED(loss);
     PPO_NEED(work);
-
-    PpoArgs a = make_args(d, b);
-    actor_grid(a.M, a.rows_per_block, a.nblocks);
-    // the reference's Python scalars 1 - margin, 1 + margin and ent_const meet
-    // fp32 tensors: rounded to fp32 once
-    a.clip_lo = (float)(1.0 - epsilon);
-    a.clip_hi = (float)(1.0 + epsilon);
-    a.ent_f = (float)ent_const;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(actor_pass, dim3((unsigned)a.nblocks), dim3(kThreads),
-                       actor_lds_bytes(a.D), s, a);
-    const int nS = 4 * (a.D + 1) + 2;
-    const int groups = nS >= kThreads ? 1 : kThreads / nS;
-    const size_t fin_lds = sizeof(double) * (size_t)nS * (1 + (groups > 1 ? groups : 0));
-    hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), fin_lds, s, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
     return 0;
 }
 
-extern "C" int marlnav_ppo_critic_grad(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
-                                       double epsilon, void *stream)
+int check_critic_bufs(const MarlnavPpoBuffers *b)
 {
-    const int rc = check_dims(d);
-    if (rc) return rc;
     if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
     PPO_NEED(obs);
     PPO_NEED(values);
@@ -866,13 +974,51 @@ extern "C" int marlnav_ppo_critic_grad(const MarlnavPpoDims *d, const MarlnavPpo
     PPO_NEED(work);
     if (reinterpret_cast<uintptr_t>(b->obs) & 7u)
         return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer obs must be 8-byte aligned");
+    return 0;
+}
 
+int launch_status()
+{
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
+    return 0;
+}
+
+// checked arguments only. adv / fold NULL: the two launches of
+// marlnav_ppo_actor_grad; given: the same two with the Adam step folded in.
+int enqueue_actor(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
+                  double ent_const, const AdvArgs *adv, const FoldArgs *fold, hipStream_t s)
+{
+    PpoArgs a = make_args(d, b);
+    actor_grid(a.M, a.rows_per_block, a.nblocks);
+    // the reference's Python scalars 1 - margin, 1 + margin and ent_const meet
+    // fp32 tensors: rounded to fp32 once
+    a.clip_lo = (float)(1.0 - epsilon);
+    a.clip_hi = (float)(1.0 + epsilon);
+    a.ent_f = (float)ent_const;
+    const int nS = 4 * (a.D + 1) + 2;
+    const int groups = nS >= kThreads ? 1 : kThreads / nS;
+    const size_t fin_lds = sizeof(double) * (size_t)nS * (1 + (groups > 1 ? groups : 0));
+    if (fold) {
+        hipLaunchKernelGGL(actor_pass, dim3((unsigned)a.nblocks), dim3(kThreads),
+                           actor_lds_bytes(a.D), s, a, *adv);
+        hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), fin_lds, s, a, *fold);
+    } else {
+        hipLaunchKernelGGL(actor_pass, dim3((unsigned)a.nblocks), dim3(kThreads),
+                           actor_lds_bytes(a.D), s, a);
+        hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), fin_lds, s, a);
+    }
+    return launch_status();
+}
+
+int enqueue_critic(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
+                   const AdvArgs *adv, const FoldArgs *fold, hipStream_t s)
+{
     PpoArgs a = make_args(d, b);
     const int AD = a.A * a.D;
     const CriticTiling ct = critic_tiling(AD, a.H);
     critic_grid(a.N, AD, a.H, ct, a.rows_per_block, a.nblocks);
     a.eps_f = (float)epsilon;  // values - epsilon: a Python scalar against an fp32 tensor
-    hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)a.nblocks, (unsigned)(ct.ncoltile * ct.nugroup));
     const int vec4 = AD % 4 == 0 && (reinterpret_cast<uintptr_t>(b->obs) & 15u) == 0;
     if (critic_split(a.N, a.H, ct)) {
@@ -888,9 +1034,13 @@ extern "C" int marlnav_ppo_critic_grad(const MarlnavPpoDims *d, const MarlnavPpo
         critic_forward_grid(a.N, a.fw_rows, a.fw_blocks);
         a.fw_part = b->work + a.nblocks * critic_stride(AD, a.H);
         float *dhbuf = reinterpret_cast<float *>(a.fw_part + a.fw_blocks * (2 * a.H + 2));
-        hipLaunchKernelGGL((critic_pass<1, kForward>),
-                           dim3((unsigned)a.fw_blocks, (unsigned)fw.nugroup), dim3(kThreads),
-                           kCriticLdsBytes, s, a, fw, dhbuf, hp, vec4);
+        const dim3 fgrid((unsigned)a.fw_blocks, (unsigned)fw.nugroup);
+        if (fold)
+            hipLaunchKernelGGL((critic_pass<1, kForward>), fgrid, dim3(kThreads),
+                               kCriticLdsBytes, s, a, fw, dhbuf, hp, vec4, *adv);
+        else
+            hipLaunchKernelGGL((critic_pass<1, kForward>), fgrid, dim3(kThreads), kCriticLdsBytes,
+                               s, a, fw, dhbuf, hp, vec4);
         if (ct.jt == 8)
             hipLaunchKernelGGL((critic_pass<8, kBackward>), grid, dim3(kThreads), kCriticLdsBytes,
                                s, a, ct, dhbuf, hp, vec4);
@@ -898,16 +1048,109 @@ extern "C" int marlnav_ppo_critic_grad(const MarlnavPpoDims *d, const MarlnavPpo
             hipLaunchKernelGGL((critic_pass<64, kBackward>), grid, dim3(kThreads), kCriticLdsBytes,
                                s, a, ct, dhbuf, hp, vec4);
     } else if (ct.jt == 8) {
-        hipLaunchKernelGGL((critic_pass<8, kFused>), grid, dim3(kThreads), kCriticLdsBytes, s, a, ct,
-                           (float *)nullptr, 0, vec4);
+        if (fold)
+            hipLaunchKernelGGL((critic_pass<8, kFused>), grid, dim3(kThreads), kCriticLdsBytes,
+                               s, a, ct, (float *)nullptr, 0, vec4, *adv);
+        else
+            hipLaunchKernelGGL((critic_pass<8, kFused>), grid, dim3(kThreads), kCriticLdsBytes, s,
+                               a, ct, (float *)nullptr, 0, vec4);
     } else {
-        hipLaunchKernelGGL((critic_pass<64, kFused>), grid, dim3(kThreads), kCriticLdsBytes, s, a,
-                           ct, (float *)nullptr, 0, vec4);
+        if (fold)
+            hipLaunchKernelGGL((critic_pass<64, kFused>), grid, dim3(kThreads), kCriticLdsBytes,
+                               s, a, ct, (float *)nullptr, 0, vec4, *adv);
+        else
+            hipLaunchKernelGGL((critic_pass<64, kFused>), grid, dim3(kThreads), kCriticLdsBytes, s,
+                               a, ct, (float *)nullptr, 0, vec4);
     }
     const int64_t nout = critic_stride(AD, a.H);
-    hipLaunchKernelGGL(critic_finish, dim3((unsigned)((nout + kThreads - 1) / kThreads)),
-                       dim3(kThreads), 0, s, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
-    return 0;
+    const dim3 ogrid((unsigned)((nout + kThreads - 1) / kThreads));
+    if (fold)
+        hipLaunchKernelGGL(critic_finish, ogrid, dim3(kThreads), 0, s, a, *fold);
+    else
+        hipLaunchKernelGGL(critic_finish, ogrid, dim3(kThreads), 0, s, a);
+    return launch_status();
+}
+
+}  // namespace
+
+extern "C" int marlnav_ppo_actor_grad(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                                      double epsilon, double ent_const, void *stream)
+{
+    int rc = check_dims(d);
+    if (rc) return rc;
+    rc = check_actor_bufs(b);
+    if (rc) return rc;
+    return enqueue_actor(d, b, epsilon, ent_const, nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int marlnav_ppo_critic_grad(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                                       double epsilon, void *stream)
+{
+    int rc = check_dims(d);
+    if (rc) return rc;
+    rc = check_critic_bufs(b);
+    if (rc) return rc;
+    return enqueue_critic(d, b, epsilon, nullptr, nullptr, (hipStream_t)stream);
+}
+
+// actor_finish is one block: its folded update walks the actor's elements
+// 256 at a time, about 4 us per 1000 elements, against the 5 us the two
+// launches of marlnav_adam_step cost. Measured: a gain of
+// 1.3-2 us per update at 854 elements (3 x 3, H = 50), 0.5 us at 1354 (3 x 8),
+// a loss of 14 us at 5054 (16 x 32). So the actor folds up to 1024 elements
+// and keeps the separate Adam launches beyond. critic_finish is thread =
+// element over many blocks; its fold gains 4-6 us per update up to 131 072
+// env rows and loses 2-3 us at 524 288 (65536 x 3 x 3 of 8 steps), where the
+// pass runs for 270 us and the separate Adam launches' dispatch hides behind
+// it: the critic folds up to 2^17 env rows.
+constexpr int64_t kActorFoldMaxElements = 1024;
+constexpr int64_t kCriticFoldMaxRows = (int64_t)1 << 17;
+
+// One minibatch update for marlnav_ppo_train_phase (marlnav_adam.hip), which
+// has checked the Adam arguments and that the table is this network's own.
+// network 0: the actor, 1: the critic. check_only: the dims and buffer checks
+// of this update and nothing launched. Returns 0 with the Adam step folded
+// into the finish launch, 1 with the gradient launches alone enqueued (the
+// caller then enqueues the Adam step), negative on an error.
+__attribute__((visibility("hidden"))) int marlnav_internal_ppo_fold(
+    int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
+    double ent_const, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, void *stream,
+    int check_only)
+{
+    int rc = check_dims(d);
+    if (rc) return rc;
+    rc = network == 0 ? check_actor_bufs(b) : check_critic_bufs(b);
+    if (rc || check_only) return rc;
+    if (network == 0) {
+        const int64_t H = d->hidden_size, D = d->obs_dim;
+        if (H * (D + 1) + 4 * H + 4 > kActorFoldMaxElements) {
+            rc = enqueue_actor(d, b, epsilon, ent_const, nullptr, nullptr, (hipStream_t)stream);
+            return rc ? rc : 1;
+        }
+    } else if (d->num_steps * d->num_parallel > kCriticFoldMaxRows) {
+        rc = enqueue_critic(d, b, epsilon, nullptr, nullptr, (hipStream_t)stream);
+        return rc ? rc : 1;
+    }
+    AdvArgs adv;
+    adv.state = static_cast<AdamState *>(ab->state);
+    adv.lr = ad->lr;
+    adv.beta1 = ad->beta1;
+    adv.beta2 = ad->beta2;
+    FoldArgs f;
+    for (int i = 0; i < 6; ++i) {
+        const bool used = i < ad->num_tensors;
+        f.param[i] = used ? ab->param[i] : nullptr;
+        f.exp_avg[i] = used ? ab->exp_avg[i] : nullptr;
+        f.exp_avg_sq[i] = used ? ab->exp_avg_sq[i] : nullptr;
+    }
+    f.state = adv.state;
+    f.beta1 = ad->beta1;
+    f.beta2 = ad->beta2;
+    f.omb1 = 1.0 - ad->beta1;
+    f.omb2 = 1.0 - ad->beta2;
+    f.eps = ad->eps;
+    f.maximize = ad->maximize;
+    if (network == 0)
+        return enqueue_actor(d, b, epsilon, ent_const, &adv, &f, (hipStream_t)stream);
+    return enqueue_critic(d, b, epsilon, &adv, &f, (hipStream_t)stream);
 }

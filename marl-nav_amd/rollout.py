@@ -373,6 +373,18 @@ def collect_fused(env, policy, buffer, eps=None, gamma=0.9):
     stream capture unless ``env.allow_graph_capture`` is set (then the
     episode counters are left alone and the stats are None: reading them
     would synchronise)."""
+    mean, capturing = _collect_fused_enqueue(env, policy, buffer, eps, gamma)
+    if capturing:
+        return mean, None
+    trunc, col, tar = env._counter_totals()                # one read of the three counters
+    env._num_trunc = env._num_col = env._num_tar = 0      # models.py:153-158
+    return mean, {"trunc": trunc, "col": col, "tar": tar}
+
+
+def _collect_fused_enqueue(env, policy, buffer, eps=None, gamma=0.9):
+    """``collect_fused`` up to the episode counters, which are left alone:
+    every check, the one C call and the host-side bookkeeping, with nothing
+    that synchronises. -> (mean_rew, capturing)."""
     who = "collect_fused"
     if env._rng != 'native' or env._init_sampler is not env._default_init_sampler:
         raise RuntimeError(f"{who} needs an env in native-RNG mode with its default init "
@@ -433,12 +445,7 @@ def collect_fused(env, policy, buffer, eps=None, gamma=0.9):
     buffer.commit(T)
     buffer.returns = returns
     env._reinit_mask = torch.where(buffer.stacked(buffer.DONE)[T - 1], 1, 0)   # environment.py:102
-    mean = stats[0]
-    if capturing:
-        return mean, None
-    trunc, col, tar = env._counter_totals()                # one read of the three counters
-    env._num_trunc = env._num_col = env._num_tar = 0      # models.py:153-158
-    return mean, {"trunc": trunc, "col": col, "tar": tar}
+    return stats[0], capturing
 
 
 def minibatch_bounds(buffer_len, batch_size):

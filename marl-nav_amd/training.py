@@ -1,0 +1,436 @@
+"""The training mode: the reference's ``MAPPO`` (marlnav/models.py:59-316)
+and its loop (marlnav/__main__.py:23-27) with every phase enqueued on the
+device by one C call and nothing read back until the logs are asked for
+(DESIGN.md §14).
+
+* ``Actor(input_size, hidden_size)`` / ``Critic(input_size, hidden_size)`` -
+  the reference's modules (models.py:14-56) written from their contract: the
+  attribute names, shapes and orthogonal weight init, so ``state_dict()``s move
+  to and from the reference's modules and ``FusedActor.from_state_dict``.
+* ``MAPPO(params, env)`` - the reference class's surface. ``get_data()`` is
+  ``collect_fused`` plus the mean-reward and episode-counter logs and the
+  checkpoint rule (libmarlnav.so ``marlnav_params_snapshot_if``), all on the
+  device; ``train_actor()`` / ``train_critic()`` are one
+  ``marlnav_ppo_train_phase`` call each; ``repeat()`` is the three in the
+  reference's order with no host synchronisation from entry to return.
+* ``train_phase(ppo, buffer, adam, network, num_epochs, batch_size)`` - the
+  phase call alone, over any ``FusedPPO`` / ``RolloutBuffer`` / ``FusedAdam``.
+* ``write_stats(logs, full_params, out_dir, stamp)`` - ``MAPPO.save_stats``
+  (models.py:200-268) on a ``_logs`` dict: the four CSVs, ``_params.json`` and
+  the four figures under the reference's file names.
+"""
+import csv
+import ctypes
+import json
+import os
+from datetime import datetime
+
+import torch
+from torch import nn
+
+from . import abi, rollout
+from .rollout import FusedAdam, FusedPolicy, FusedPPO, RolloutBuffer, minibatch_bounds
+from .utils import ActionScaler, ObsNormalizer
+
+_F64 = torch.float64
+ACTOR_KEYS = ("fc1.weight", "fc1.bias", "fc_mu.weight", "fc_mu.bias", "fc_std.weight",
+              "fc_std.bias")
+CRITIC_KEYS = ("fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
+
+
+class Actor(nn.Module):
+    """models.py:14-36: ``fc1`` (no activation), then ``tanh(fc_mu)`` as the
+    mean and ``softplus(fc_std)`` as the covariance diagonal of a
+    ``MultivariateNormal`` over the flattened agent rows."""
+
+    def __init__(self, input_size, hidden_size):
+        super().__init__()
+        self.fc1 = nn.Linear(input_size, hidden_size)
+        self.fc_mu = nn.Linear(hidden_size, 2)
+        self.fc_std = nn.Linear(hidden_size, 2)
+        for m in (self.fc1, self.fc_mu, self.fc_std):
+            nn.init.orthogonal_(m.weight)
+
+    def forward(self, x):
+        x = self.fc1(x.flatten(0, 1))
+        mu = torch.tanh(self.fc_mu(x))
+        var = nn.functional.softplus(self.fc_std(x))
+        return torch.distributions.MultivariateNormal(mu, torch.diag_embed(var))
+
+
+class Critic(nn.Module):
+    """models.py:39-56: ``fc2(relu(fc1(x)))`` over the env's flattened rows."""
+
+    def __init__(self, input_size, hidden_size):
+        super().__init__()
+        self.fc1 = nn.Linear(input_size, hidden_size)
+        self.fc2 = nn.Linear(hidden_size, 1)
+        for m in (self.fc1, self.fc2):
+            nn.init.orthogonal_(m.weight)
+
+    def forward(self, x):
+        return self.fc2(torch.relu(self.fc1(x.flatten(1))))
+
+
+def _empty_logs():
+    return {'epi_stats': {'trunc': [], 'col': [], 'tar': []}, 'mean_rews': [], 'actor': [],
+            'critic': []}
+
+
+def stats_paths(out_dir, stamp):
+    """The reference's file names (models.py:84-92, 202-222) under
+    ``out_dir``: -> dict of the two weight files, the four figures, the four
+    CSVs and the params file."""
+    w, p, l = (os.path.join(out_dir, d) for d in ('weights', 'plots', 'logs'))
+    return {'actor': os.path.join(w, stamp + '_actor.pt'),
+            'critic': os.path.join(w, stamp + '_critic.pt'),
+            'rew_plot': os.path.join(p, stamp + '_mean_rews.png'),
+            'act_plot': os.path.join(p, stamp + '_act_loss.png'),
+            'cri_plot': os.path.join(p, stamp + '_cri_loss.png'),
+            'epi_plot': os.path.join(p, stamp + '_epi_stats.png'),
+            'params': os.path.join(l, stamp + '_params.json'),
+            'rew_log': os.path.join(l, stamp + '_mean_rews.csv'),
+            'act_log': os.path.join(l, stamp + '_act_loss.csv'),
+            'cri_log': os.path.join(l, stamp + '_cri_loss.csv'),
+            'epi_log': os.path.join(l, stamp + '_epi_stats.csv')}
+
+
+def write_stats(logs, full_params, out_dir, stamp, plot=True):
+    """``MAPPO.save_stats`` (models.py:200-268) for a ``_logs`` dict of Python
+    numbers: ``logs/<stamp>_params.json`` (indent 4, sorted keys; what json
+    cannot write goes through ``str``), the three one-column CSVs (header
+    ``Value``) and ``_epi_stats.csv`` (``Truncated, Collisions, Target
+    reached``), and with ``plot`` the four figures under ``plots/``. Returns
+    the paths written."""
+    paths = stats_paths(out_dir, stamp)
+    os.makedirs(os.path.dirname(paths['params']), exist_ok=True)
+    with open(paths['params'], 'w') as f:
+        json.dump(full_params, f, indent=4, sort_keys=True, default=str)
+    for key, name in (('mean_rews', 'rew_log'), ('actor', 'act_log'), ('critic', 'cri_log')):
+        with open(paths[name], 'w', newline='') as f:
+            writer = csv.writer(f)
+            writer.writerow(['Value'])
+            writer.writerows([[num] for num in logs[key]])
+    epi = logs['epi_stats']
+    with open(paths['epi_log'], 'w', newline='') as f:
+        writer = csv.writer(f)
+        writer.writerow(['Truncated', 'Collisions', 'Target reached'])
+        writer.writerows([[epi['trunc'][i], epi['col'][i], epi['tar'][i]]
+                          for i in range(len(epi['trunc']))])
+    written = [paths[k] for k in ('params', 'rew_log', 'act_log', 'cri_log', 'epi_log')]
+    if not plot:
+        return written
+    import matplotlib
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    os.makedirs(os.path.dirname(paths['rew_plot']), exist_ok=True)
+    for key, xlabel, title, name in (('mean_rews', 'rollot_num', 'Mean Rewards', 'rew_plot'),
+                                     ('actor', 'batch_num', 'Actor Losses', 'act_plot'),
+                                     ('critic', 'batch_num', 'Critic Losses', 'cri_plot')):
+        fig, ax = plt.subplots(1, 1)
+        ax.set(xlabel=xlabel, ylabel='value')
+        ax.plot(logs[key])
+        fig.suptitle(title)
+        fig.savefig(paths[name])
+        plt.close(fig)
+    fig, ax = plt.subplots(1, 1)
+    ax.set(xlabel='rollout', ylabel='value')
+    ax.plot(epi['trunc'], color='blue', label='truncated')
+    ax.plot(epi['col'], color='red', label='collisions')
+    ax.plot(epi['tar'], color='green', label='target reached')
+    ax.legend()
+    fig.suptitle('Episode endings')
+    fig.savefig(paths['epi_plot'])
+    plt.close(fig)
+    return written + [paths[k] for k in ('rew_plot', 'act_plot', 'cri_plot', 'epi_plot')]
+
+
+def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None):
+    """One whole ``train_actor`` (``network='actor'``) or ``train_critic``
+    (``'critic'``) of the reference (models.py:160-198) over ``buffer`` as ONE
+    C call, libmarlnav.so ``marlnav_ppo_train_phase``: ``num_epochs`` times
+    the minibatches of ``minibatch_bounds(len(buffer), batch_size)``, an
+    update's Adam step folded into the gradient kernels' finish launch where
+    that was measured to be faster.
+    Bit for bit what ``rollout.train_actor`` / ``train_critic`` leave with the
+    same ``FusedAdam``: losses, ``.grad``, parameters, moments, step count.
+
+    ``ppo``: a ``FusedPPO``; ``adam``: a ``FusedAdam`` over exactly that
+    network's parameters in ``_POLICY_PARAMS`` order (the library refuses any
+    other table). ``out``: a contiguous float64 device tensor of
+    ``num_epochs * len(bounds)`` elements for the losses in update order
+    (allocated where None); returned. Nothing synchronises."""
+    nets = {'actor': abi.NETWORK_ACTOR, 'critic': abi.NETWORK_CRITIC,
+            abi.NETWORK_ACTOR: abi.NETWORK_ACTOR, abi.NETWORK_CRITIC: abi.NETWORK_CRITIC}
+    if network not in nets:
+        raise ValueError(f"network must be 'actor' or 'critic', got {network!r}")
+    if buffer.returns is None:
+        raise RuntimeError("the rollout buffer has no returns yet: call "
+                           "buffer.process_rewards(gamma) (or collect()) before training")
+    lib, dev = ppo._lib, ppo.device
+    bounds = minibatch_bounds(len(buffer), batch_size)
+    B, E = len(bounds), int(num_epochs)
+    if B < 1:
+        raise ValueError(f"batch_size={batch_size} is greater than the {len(buffer)} stored "
+                         "steps: no minibatch")
+    if E < 1:
+        raise ValueError(f"num_epochs={num_epochs} must be >= 1")
+    if out is None:
+        out = torch.empty(E * B, dtype=_F64, device=dev)
+    if (out.dtype != _F64 or out.device != dev or out.numel() != E * B
+            or not out.is_contiguous()):
+        raise ValueError(f"out: need a contiguous float64 tensor of {E * B} elements on {dev}")
+    arr = (ctypes.c_int64 * (2 * B))(*[x for b in bounds for x in b])
+    ppo._bind(buffer, 0, len(buffer))       # step 0 of the storage, dims of the whole buffer
+    d, b = ppo._dims, ppo._bufs
+    need = int(lib.marlnav_ppo_train_work_size(ctypes.byref(d), arr, B))
+    if need < 0:
+        abi.check(need, lib)
+    if ppo._work.numel() < need:
+        ppo._work = torch.empty(need, dtype=_F64, device=dev)
+    b.work = ppo._work.data_ptr()
+    ad, ab = adam._bind()
+    abi.check(lib.marlnav_ppo_train_phase(
+        nets[network], ctypes.byref(d), ctypes.byref(b), arr, B, E, ppo.epsilon, ppo.ent_const,
+        ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(),
+        torch._C._cuda_getCurrentRawStream(dev.index)), lib)
+    return out
+
+
+class MAPPO(object):
+    """The reference's ``MAPPO(params, env)`` (models.py:59-104) on the
+    device. ``params`` is ``utils.set_model_params``'s dict; ``env`` a
+    ``marlnav_amd.Env`` in native-RNG mode with its default init sampler.
+    Refused at construction, as ``collect_fused`` refuses them at its call: a
+    reference-RNG env or one with a user-assigned sampler, and an env with no
+    normaliser / action scaler where ``params`` has none to attach
+    (``params['normalizer']`` / ``params['scaler']`` are attached to an env
+    that has none, as ``--evaluate`` does).
+
+    ``seed`` keys the policy kernel's normals (``FusedPolicy``); the modules'
+    initial weights come from torch's global generator, as the reference's do.
+
+    The checkpoint rule and its quirk. The reference saves both state dicts
+    after a rollout whose mean reward exceeds ``_max_rew`` (models.py:127-129)
+    and never updates ``_max_rew`` from ``-inf``: it saves after EVERY rollout
+    whose mean is not NaN, and since the save happens in ``get_data``, before
+    that repeat's training, the files left by a run hold the weights from
+    before the last repeat's training. ``track_best=False`` (the default)
+    reproduces exactly that; ``track_best=True`` keeps the maximum, so the
+    files hold the weights that produced the best rollout. Here the save is a
+    device-side copy into a snapshot allocation (``marlnav_params_snapshot_if``)
+    and ``save_weights()`` writes that snapshot to the reference's two files.
+
+    ``out_dir``: where ``weights/``, ``plots/`` and ``logs/`` are created
+    (the reference uses the working directory), at the first write."""
+
+    def __init__(self, params, env, seed=0, track_best=False, out_dir='.'):
+        who = "MAPPO"
+        if env._rng != 'native' or env._init_sampler is not env._default_init_sampler:
+            raise RuntimeError(f"{who} needs an env in native-RNG mode with its default init "
+                               "sampler: a reference-RNG or user-assigned sampler is called on "
+                               "the host every step")
+        if env._normalizer is None and params.get('normalizer') is not None:
+            env.attach_normalizer(ObsNormalizer(params['normalizer']))
+        if env._action_scaler is None and params.get('scaler') is not None:
+            env.attach_action_scaler(ActionScaler(params['scaler']))
+        if env._normalizer is None or env._action_scaler is None:
+            raise RuntimeError(f"{who} needs an observation normaliser and an action scaler: "
+                               "params['normalizer'] / params['scaler'], or "
+                               "env.attach_normalizer(...) / env.attach_action_scaler(...)")
+        # the env's C parameters now (the action scaler's two tensors are read
+        # back once): the first repeat() then has nothing left that synchronises
+        env._sync_params()
+        self.num_agents = params['num_agents']
+        self.num_parallel = params['num_parallel']
+        self.action_size = params['action_size']
+        self.device = torch.device(env.device)
+        if self.device.type != 'cuda':
+            raise RuntimeError(f"{who} runs on a HIP device (no CPU fallback); the env is on "
+                               f"{self.device}")
+        self.env = env
+        self.actor = Actor(**params['actor']).to(self.device)
+        self.critic = Critic(**params['critic']).to(self.device)
+        self.actor_optimizer = FusedAdam(self.actor.parameters(), lr=params['lr'], maximize=True)
+        self.critic_optimizer = FusedAdam(self.critic.parameters(), lr=params['lr'],
+                                          maximize=False)
+        self.ent_const = params['ent_const']
+        self.epsilon = params['epsilon']
+        self.gamma = params['gamma']
+        self.buffer_len = int(params['buffer_len'])
+        self.num_epochs = int(params['num_epochs'])
+        self.batch_size = int(params['batch_size'])
+        if self.num_epochs < 1:
+            raise ValueError(f"num_epochs={self.num_epochs} must be >= 1")
+        self._bounds = minibatch_bounds(self.buffer_len, self.batch_size)
+        if not self._bounds:
+            raise ValueError(f"batch_size={self.batch_size} is greater than "
+                             f"buffer_len={self.buffer_len}: no minibatch")
+        self.buffer = RolloutBuffer(self.buffer_len)
+        self.policy = FusedPolicy(self.actor, self.critic, seed=seed)
+        self.ppo = FusedPPO(self.actor, self.critic, self.epsilon, self.ent_const)
+        self.track_best = bool(track_best)
+        self.out_dir = out_dir
+        self._time = datetime.now().strftime('%Y%m%d%H%M%S')
+        paths = stats_paths(out_dir, self._time)
+        self._actor_path, self._critic_path = paths['actor'], paths['critic']
+        self._lib = abi.load_library()
+        dev = self.device
+        self._mean_rew = None
+        self._max_rew = torch.full((1,), float('-inf'), dtype=_F64, device=dev)
+        self._save_state = torch.tensor([0, -1], dtype=torch.int64, device=dev)
+        # the snapshot of the ten parameters: one flat allocation, segments on 16 bytes
+        self._live = [t for _, t in self.policy._params]
+        offs, at = [], 0
+        for t in self._live:
+            offs.append(at)
+            at += (t.numel() + 3) // 4 * 4
+        self._snap_flat = torch.zeros(at, dtype=torch.float32, device=dev)
+        self._snapshot = [self._snap_flat[o:o + t.numel()].view(t.shape)
+                          for o, t in zip(offs, self._live)]
+        n = len(self._live)
+        self._snap_src = (ctypes.c_void_p * n)(*[t.data_ptr() for t in self._live])
+        self._snap_dst = (ctypes.c_void_p * n)(*[t.data_ptr() for t in self._snapshot])
+        self._snap_numel = (ctypes.c_int64 * n)(*[t.numel() for t in self._live])
+        self._r = 0                         # rollouts collected
+        total = params.get('num_total')
+        self._cap = 0
+        self._mean_log = self._epi_log = self._actor_log = self._critic_log = None
+        self._reserve(max(1, int(total) // (self.buffer_len * self.num_parallel)) if total else 1)
+        self._logs = _empty_logs()
+
+    # ------------------------------------------------------------- the logs
+    def _reserve(self, repeats):
+        """Device logs for ``repeats`` rollouts: rows are kept when they grow
+        (a device copy, nothing synchronises)."""
+        if repeats <= self._cap:
+            return
+        cap = max(repeats, 2 * self._cap)
+        U = self.num_epochs * len(self._bounds)
+        new = (torch.zeros(cap, dtype=_F64, device=self.device),
+               torch.zeros(cap, 3, dtype=torch.int64, device=self.device),
+               torch.zeros(cap, U, dtype=_F64, device=self.device),
+               torch.zeros(cap, U, dtype=_F64, device=self.device))
+        old = (self._mean_log, self._epi_log, self._actor_log, self._critic_log)
+        if self._cap:
+            for n, o in zip(new, old):
+                n[:self._cap].copy_(o)
+        self._mean_log, self._epi_log, self._actor_log, self._critic_log = new
+        self._cap = cap
+
+    def logs(self):
+        """The reference's ``_logs`` layout (models.py:95-104) with Python
+        numbers, for the rollouts collected so far: ``epi_stats`` (``trunc`` /
+        ``col`` / ``tar``, one int per rollout), ``mean_rews`` (one float per
+        rollout), ``actor`` / ``critic`` (one loss per update, in order; a
+        rollout that was not trained on contributes zeros). Synchronises once:
+        the device logs travel as one float64 tensor (the counters are exact
+        below 2^53). Also kept as ``self._logs``."""
+        r = self._r
+        U = self._actor_log.shape[1]
+        flat = torch.cat([self._mean_log[:r], self._epi_log[:r].to(_F64).flatten(),
+                          self._actor_log[:r].flatten(), self._critic_log[:r].flatten(),
+                          self._save_state.to(_F64)]).cpu()
+        mean, epi, act, cri, save = torch.split(flat, [r, 3 * r, r * U, r * U, 2])
+        epi = epi.view(r, 3).to(torch.int64).tolist()
+        self._saves = (int(save[0]), int(save[1]))
+        self._logs = {'epi_stats': {'trunc': [e[0] for e in epi], 'col': [e[1] for e in epi],
+                                    'tar': [e[2] for e in epi]},
+                      'mean_rews': mean.tolist(), 'actor': act.tolist(), 'critic': cri.tolist()}
+        return self._logs
+
+    def save_count(self):
+        """(number of snapshots taken, repeat index of the last one or -1).
+        Synchronises."""
+        s = self._save_state.tolist()
+        return int(s[0]), int(s[1])
+
+    # ----------------------------------------------------------- the phases
+    def _stream(self):
+        return torch._C._cuda_getCurrentRawStream(self.device.index)
+
+    def get_data(self):
+        """models.py:106-129: one rollout of ``buffer_len`` steps into
+        ``buffer`` (``collect_fused``'s one C call), its mean reward into row
+        r of the device log, the three episode counters' totals into row r of
+        theirs and the counters zeroed (models.py:151-158), then the
+        checkpoint rule (the class docstring). Nothing synchronises and
+        nothing is printed."""
+        r = self._r
+        self._reserve(r + 1)
+        env, lib = self.env, self._lib
+        mean, _ = rollout._collect_fused_enqueue(env, self.policy, self.buffer, gamma=self.gamma)
+        self._mean_rew = mean
+        self._mean_log[r].copy_(mean)
+        abi.check(lib.marlnav_counters_total(ctypes.byref(env._dims), env._counters.data_ptr(),
+                                             self._epi_log[r].data_ptr(), self._stream()), lib)
+        env._counters.zero_()
+        abi.check(lib.marlnav_params_snapshot_if(
+            len(self._live), self._snap_src, self._snap_dst, self._snap_numel,
+            self._mean_log[r].data_ptr(), self._max_rew.data_ptr(), self._save_state.data_ptr(),
+            r, 1 if self.track_best else 0, self._stream()), lib)
+        self._r = r + 1
+
+    def _phase(self, network, adam, log):
+        if self._r < 1:
+            raise RuntimeError("no rollout to train on yet: call get_data() first")
+        train_phase(self.ppo, self.buffer, adam, network, self.num_epochs, self.batch_size,
+                    out=log[self._r - 1])
+
+    def train_actor(self):
+        """models.py:160-178 for the last rollout as ONE C call
+        (``marlnav_ppo_train_phase``): ``num_epochs`` times the minibatches of
+        ``minibatch_bounds(buffer_len, batch_size)``, each update's loss into
+        the device log. Nothing is printed and nothing synchronises."""
+        self._phase(abi.NETWORK_ACTOR, self.actor_optimizer, self._actor_log)
+
+    def train_critic(self):
+        """models.py:180-198, as ``train_actor``."""
+        self._phase(abi.NETWORK_CRITIC, self.critic_optimizer, self._critic_log)
+
+    def repeat(self):
+        """One pass of the reference's loop body (__main__.py:25-27):
+        ``get_data``, ``train_actor``, ``train_critic``; no host
+        synchronisation from entry to return."""
+        self.get_data()
+        self.train_actor()
+        self.train_critic()
+
+    def run(self, num_repeats, save_every=None):
+        """``num_repeats`` repeats; ``save_weights()`` at the end and, with
+        ``save_every=N``, after every N-th repeat. Returns the two paths (or
+        None where no snapshot was ever taken)."""
+        num_repeats = int(num_repeats)
+        self._reserve(self._r + num_repeats)
+        for i in range(num_repeats):
+            self.repeat()
+            if save_every and (i + 1) % int(save_every) == 0 and i + 1 < num_repeats:
+                self.save_weights()
+        return self.save_weights()
+
+    # ------------------------------------------------------------ the files
+    def snapshot_state_dicts(self):
+        """The snapshot as the two state dicts with the reference's keys (CPU
+        copies)."""
+        cpu = [t.detach().cpu().clone() for t in self._snapshot]
+        return dict(zip(ACTOR_KEYS, cpu[:6])), dict(zip(CRITIC_KEYS, cpu[6:]))
+
+    def save_weights(self):
+        """Write the snapshot as ``weights/<time>_actor.pt`` and
+        ``_critic.pt`` (state dicts with the reference's keys, as models.py:
+        128-129 saves them) -> (actor path, critic path); None, with nothing
+        written, where no snapshot was taken yet (the reference has no files
+        then either). With ``track_best=False`` the files hold the weights
+        from BEFORE the last repeat's training, as the reference's do at the
+        same moment (the class docstring). Synchronises."""
+        if self.save_count()[0] < 1:
+            return None
+        actor, critic = self.snapshot_state_dicts()
+        os.makedirs(os.path.dirname(self._actor_path), exist_ok=True)
+        torch.save(actor, self._actor_path)
+        torch.save(critic, self._critic_path)
+        return self._actor_path, self._critic_path
+
+    def save_stats(self, full_params, plot=True):
+        """models.py:200-268: ``write_stats`` of ``logs()``."""
+        return write_stats(self.logs(), full_params, self.out_dir, self._time, plot=plot)

@@ -158,6 +158,40 @@ def set_env_params(args, device):
     return p
 
 
+def set_model_params(args, device):
+    """utils.py:155-191: the ``MAPPO(params, env)`` constructor contract, with
+    the reference's two validations (``batch_size <= buffer_len``;
+    ``num_total`` divisible by ``buffer_len * num_parallel``).
+
+    Deliberate deviation: the observation size is that of the env's shape,
+    ``2 + 2 * num_obstacles + 2 * (num_agents - 1)``. The reference hard-codes
+    12, which is right for 3 agents x 3 obstacles only; at that shape the two
+    agree."""
+    if args.batch_size > args.buffer_len:
+        raise ValueError("batch_size can't be greater than buffer_len.")
+    if args.num_total % (args.buffer_len * args.num_parallel) != 0:
+        raise ValueError('num_total should be divisible with (buffer_len * num_parallel).')
+    obs_size = 2 + 2 * args.num_obstacles + 2 * (args.num_agents - 1)
+    return {
+        'actor': {'input_size': obs_size, 'hidden_size': args.hidden_size},
+        'critic': {'input_size': obs_size * args.num_agents, 'hidden_size': args.hidden_size},
+        'num_agents': args.num_agents,
+        'device': device,
+        'lr': args.learning_rate,
+        'ent_const': args.ent_const,
+        'epsilon': args.epsilon,
+        'gamma': args.gamma,
+        'num_total': args.num_total,
+        'num_parallel': args.num_parallel,
+        'buffer_len': args.buffer_len,
+        'num_epochs': args.num_epochs,
+        'batch_size': args.batch_size,
+        'action_size': 2,
+        'normalizer': set_normalizer_params(args, device),
+        'scaler': set_scaler_params(args, device),
+    }
+
+
 # ----------------------------------------------------------------- samplers
 def _formation_offsets(num_agents):
     """Agent offsets (units of ags_dist/2) of the reference's 3-agent triangle
