@@ -116,6 +116,87 @@ def list_minibatches(buffer, batch_size):
     return out
 
 
+# ------------------------------------------------------------------ launch plan
+# The host side of csrc/marlnav_ppo.hip restated: which kernels a minibatch of
+# T x P env rows of A agents, O obstacles and H hidden units launches, and on
+# what grid. tests/test_ppo_cpu.py holds it to marlnav_ppo_work_size and pins
+# every named shape of the GPU tests to the path it is there for.
+THREADS = 256
+ACTOR_TILE, ACTOR_MAX_BLOCKS, ACTOR_MIN_ROWS = 256, 1024, 1024
+CRITIC_TILE, CRITIC_TARGET_BLOCKS, CRITIC_FORWARD_BLOCKS = 64, 512, 1024
+CRITIC_MAX_WORK = 8 << 20       # fp64 elements of chunk partials
+CRITIC_MAX_DH = 32 << 20        # floats of dh shared through the workspace
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def launch_plan(T, P, A, O, H):
+    """-> {'critic': {...}, 'actor': {...}, 'work_size': doubles}.
+
+    critic: kernel ('fused8' | 'fused64' | 'split8' | 'split64'; a split one
+    is critic_pass<1, kForward> then critic_pass<8 | 64, kBackward>),
+    col_tiles, last_tile_cols, unit_slices, units_per_block, unit_groups,
+    forward_groups (unit groups of the kForward launch, 0 when fused),
+    forward_blocks, chunks, tiles_per_chunk, last_tile_rows, vec4 (what the
+    row width allows; the launch also wants obs 16-byte aligned).
+    actor: blocks, tiles_per_block, slices, col_rounds, finish_groups."""
+    D = 2 + 2 * O + 2 * (A - 1)
+    AD, N = A * D, T * P
+    M = N * A
+    # actor_grid, the phase-2 ownership of actor_pass, the groups of actor_finish
+    rows = max(_cdiv(M, ACTOR_MAX_BLOCKS), ACTOR_MIN_ROWS)
+    rows = _cdiv(rows, ACTOR_TILE) * ACTOR_TILE
+    ncol = D + 1
+    nS = 4 * ncol + 2
+    actor = {"blocks": _cdiv(M, rows), "tiles_per_block": rows // ACTOR_TILE,
+             "slices": 1 if ncol >= THREADS else THREADS // ncol,
+             "col_rounds": _cdiv(ncol, THREADS),
+             "finish_groups": 1 if nS >= THREADS else THREADS // nS}
+    actor_work = actor["blocks"] * nS
+    # critic_tiling
+    kc = min(AD, THREADS)
+    col_tiles = _cdiv(AD, kc)
+    us_n = THREADS // kc
+    jt = 8 if us_n >= 2 else 64
+    ub = us_n * jt
+    if ub > 64:
+        us_n, ub = 64 // jt, 64
+    unit_groups = _cdiv(H, ub)
+    # critic_grid
+    stride = H * AD + 2 * H + 2
+    want = max(min(CRITIC_TARGET_BLOCKS // (col_tiles * unit_groups), CRITIC_MAX_WORK // stride), 1)
+    tiles = _cdiv(N, CRITIC_TILE)
+    tiles_per_chunk = _cdiv(tiles, want)
+    chunks = _cdiv(N, tiles_per_chunk * CRITIC_TILE)
+    critic_work = chunks * stride
+    # critic_split, critic_forward_grid, dh_pitch
+    pitch = _cdiv(H, 64) * 64
+    split = col_tiles * unit_groups > 1 and N * pitch <= CRITIC_MAX_DH
+    forward_blocks = 0
+    if split:
+        frows = _cdiv(_cdiv(N, CRITIC_FORWARD_BLOCKS), CRITIC_TILE) * CRITIC_TILE
+        forward_blocks = _cdiv(N, frows)
+        critic_work += forward_blocks * (2 * H + 2) + (N * pitch + 1) // 2
+    critic = {"kernel": ("split" if split else "fused") + str(jt),
+              "col_tiles": col_tiles, "last_tile_cols": AD - (col_tiles - 1) * kc,
+              "unit_slices": us_n, "units_per_block": ub, "unit_groups": unit_groups,
+              "forward_groups": _cdiv(H, 64) if split else 0, "forward_blocks": forward_blocks,
+              "chunks": chunks, "tiles_per_chunk": tiles_per_chunk,
+              "last_tile_rows": N - (tiles - 1) * CRITIC_TILE, "vec4": AD % 4 == 0}
+    return {"critic": critic, "actor": actor, "work_size": max(actor_work, critic_work)}
+
+
+def launch_path(T, P, A, O, H):
+    """What the CPU tests pin per named shape: (critic kernel, column tiles,
+    unit groups, tiles per chunk, actor slices, actor column rounds)."""
+    p = launch_plan(T, P, A, O, H)
+    c, a = p["critic"], p["actor"]
+    return (c["kernel"], c["col_tiles"], c["unit_groups"], c["tiles_per_chunk"], a["slices"],
+            a["col_rounds"])
+
+
 # ------------------------------------------------------------------ fixture F7
 _cache = {}
 

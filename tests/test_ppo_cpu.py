@@ -3,7 +3,10 @@
 ctypes mirrors, the library exports the three entry points, argument
 validation fails loudly before any HIP call, and fixture F7-ppo pins the
 formulas and the reference's quirks (tests/ppo_ref.py) independently of the
-kernels."""
+kernels. The host side's launch plan, restated as ppo_ref.launch_plan, is held
+to marlnav_ppo_work_size, every named shape of the GPU tests is pinned to the
+launch path it is there for, and the generated cases' seeds are checked
+against their boundary margins."""
 import ctypes
 import os
 import subprocess
@@ -13,6 +16,8 @@ import pytest
 import torch
 
 import ppo_ref as pp
+import test_ppo_gpu as tg
+import test_train_gpu as tt
 from conftest import ROOT
 
 HEADER = os.path.join(ROOT, "include", "marlnav.h")
@@ -227,3 +232,96 @@ def test_minibatch_bounds_are_the_reference_slices(pkg):
             got = pkg.minibatch_bounds(n, bs)
             assert [steps[lo:hi] for lo, hi in got] == want, (n, bs)
             assert all(0 <= lo < hi <= n for lo, hi in got)
+
+
+# ------------------------------------------------------------------ launch plan
+def _named_shapes():
+    """Every (T, P, A, O, H) the GPU tests launch under a name, with the path
+    written beside it."""
+    named = [("ppo " + n, s[:5], tg.PATHS[n]) for n, s in tg.SHAPES.items()]
+    named += [("phase " + n, s[:5], tt.PHASE_PATHS[n]) for n, s in tt.PHASE_SHAPES.items()]
+    for n, (A, O, H, _) in tg.TILE_LOOP.items():
+        both, one = tg.TILE_LOOP_PATHS[n]
+        named.append(("tile loop " + n, (2, tg.TILE_LOOP_P, A, O, H), both))
+        named.append(("tile loop step " + n, (1, tg.TILE_LOOP_P, A, O, H), one))
+    return named
+
+
+def _work_size(pkg, T, P, A, O, H):
+    d = pkg.abi.MarlnavPpoDims(num_parallel=P, num_steps=T, num_agents=A,
+                               obs_dim=2 + 2 * O + 2 * (A - 1), hidden_size=H)
+    return int(pkg.abi.load_library().marlnav_ppo_work_size(ctypes.byref(d)))
+
+
+# A D -> (A, O) of the sweep: up to, at and past one block's 128 and 256
+# columns, rows that are no multiple of 4 (30, 66, 130, 258), the widest
+SWEEP_AD = {12: (2, 1), 28: (2, 5), 30: (3, 2), 64: (2, 14), 66: (3, 8), 128: (2, 30),
+            130: (5, 8), 132: (2, 31), 256: (2, 62), 258: (3, 40), 516: (2, 127),
+            40960: (64, 256)}
+SWEEP_H = (1, 8, 16, 17, 56, 57, 64, 65, 512)
+SWEEP_N = (2, 64, 65, 32768, 32769)
+
+
+def test_launch_plan_agrees_with_the_library_on_the_work_size(pkg):
+    shapes = [s for _, s, _ in _named_shapes()]
+    for AD, (A, O) in SWEEP_AD.items():
+        assert A * (2 + 2 * O + 2 * (A - 1)) == AD
+        shapes += [(1, N, A, O, H) for H in SWEEP_H for N in SWEEP_N]
+    assert len(shapes) > 12 * 9 * 5
+    kernels = set()
+    for s in shapes:
+        plan = pp.launch_plan(*s)
+        assert plan["work_size"] == _work_size(pkg, *s), s
+        kernels.add(plan["critic"]["kernel"])
+    assert kernels == {"fused8", "fused64", "split8", "split64"}
+
+
+def test_every_named_shape_takes_the_path_it_is_there_for():
+    named = _named_shapes()
+    for name, shape, path in named:
+        assert pp.launch_path(*shape) == path, (name, shape, pp.launch_path(*shape))
+    plan = {name: pp.launch_plan(*shape) for name, shape, _ in named}
+    crit = lambda n, *keys: tuple(plan[n]["critic"][k] for k in keys)
+    act = lambda n, *keys: tuple(plan[n]["actor"][k] for k in keys)
+    # what the path tuple does not show
+    assert crit("ppo chunks", "chunks") == (44,) and act("ppo chunks", "blocks") == (9,)
+    assert crit("ppo long_row", "last_tile_cols") == (4,)
+    assert crit("ppo fused64", "chunks", "last_tile_rows") == (2, 16)
+    assert crit("ppo fused64_full", "last_tile_cols", "units_per_block") == (256, 64)
+    assert crit("ppo unit_groups64", "units_per_block", "forward_groups") == (64, 2)
+    assert crit("ppo slice_cap", "unit_slices", "units_per_block") == (8, 64)
+    assert crit("ppo two_slices", "unit_slices", "units_per_block") == (2, 16)
+    assert crit("ppo h_max", "unit_slices", "units_per_block", "forward_groups") == (7, 56, 8)
+    assert crit("ppo cols255", "last_tile_cols") == (252,)
+    assert crit("ppo cols257", "last_tile_cols") == (256,)
+    assert crit("ppo two_tiles", "chunks", "last_tile_rows") == (1, 6)
+    assert crit("tile loop fused8", "chunks", "last_tile_rows") == (257, 32)
+    assert crit("tile loop fused64", "chunks", "last_tile_rows") == (257, 32)
+    assert crit("tile loop step fused64", "chunks") == (257,)
+    # between them the shapes reach every critic kernel, a second tile of a
+    # chunk in a fused and in a split kernel, several unit groups behind both
+    # backward kernels, every column regime of the actor and 2..7 row slices
+    paths = {p for _, _, p in named}
+    assert {p[0] for p in paths} == {"fused8", "fused64", "split8", "split64"}
+    assert {(p[0], p[3]) for p in paths} >= {("fused8", 2), ("fused64", 2), ("split64", 2)}
+    assert {p[0] for p in paths if p[2] > 1} == {"split8", "split64"}
+    assert {p[5] for p in paths} == {1, 2, 3}
+    assert {p[4] for p in paths} >= {1, 2, 3, 7}
+
+
+@pytest.mark.parametrize("name", list(tg.SHAPES))
+def test_generated_cases_keep_their_margins(name):
+    """``generated`` asserts the GAPS / MARGIN conditions of its case (and
+    that the fp32 and fp64 evaluations take the same branches) on the CPU:
+    the seeds written beside the shapes are valid before any GPU runs."""
+    which = tg.WHICH.get(name, tg.BOTH)
+    w, data, truth, ref = tg.generated(*tg.SHAPES[name], which=which)
+    assert set(truth) == set(ref) == set(which)
+    # what the seeds were picked on (tg.SHAPES), printed: the reference's fp32
+    # loss error on this host beside the rounding level of its stored values
+    levels = tg.loss_rounding_levels(w, data, which)
+    for net in which:
+        l64, l32 = float(truth[net][0]), float(ref[net][0])
+        assert np.isfinite(l64) and np.isfinite(levels[net]) and levels[net] > 0
+        print(f"{name} {net} loss: reference {abs(l32 - l64) / abs(l64):.3e}  "
+              f"rounding level {levels[net]:.3e}")

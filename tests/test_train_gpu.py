@@ -131,6 +131,20 @@ PHASE_SHAPES = {
     "wide": (2, 3, 16, 32, 7, 101),         # six column tiles, the critic's own forward launch
     "mid_row": (2, 16, 16, 48, 5, 303),
     "long_row": (2, 64, 2, 127, 3, 404),    # D + 1 > 256
+    "fused64": (2, 40, 4, 13, 50, 2),       # critic_pass<64, kFused> with the count's advance
+    "unit_groups64": (2, 40, 2, 31, 65, 1),  # folded critic_finish behind 2 forward unit groups
+}
+# the path of each, as test_ppo_gpu.PATHS (pinned by tests/test_ppo_cpu.py)
+PHASE_PATHS = {
+    "tiny": ("fused8", 1, 1, 1, 19, 1),
+    "fold_last": ("split8", 1, 2, 1, 19, 1),
+    "fold_first_out": ("split8", 1, 2, 1, 19, 1),
+    "chunks": ("fused8", 1, 1, 1, 19, 1),
+    "wide": ("split64", 6, 1, 1, 2, 1),
+    "mid_row": ("split64", 8, 1, 1, 1, 1),
+    "long_row": ("split64", 3, 1, 1, 1, 2),
+    "fused64": ("fused64", 1, 1, 1, 7, 1),
+    "unit_groups64": ("split64", 1, 2, 1, 3, 1),
 }
 
 
