@@ -197,6 +197,36 @@ int marlnav_discounted_returns(const float *rewards, const uint8_t *done, int64_
                                int64_t P, double gamma, double *returns, double *stats,
                                double *work, void *stream);
 
+/* GAE(lambda) advantages of a rollout of T steps (not in the
+ * reference, whose estimator is the normalised return above). One thread per
+ * env walks its column backwards in fp64 in this operation order, with
+ * gl = gamma * lam formed once on the host in fp64 and A_next = 0 at t = T-1:
+ *   next  = t == T-1 ? (double)last_values[p] : (double)values[t+1][p]
+ *   delta = ((double)r + gamma * (done ? 0.0 : next)) - (double)v
+ *   A     = delta + gl * (done ? 0.0 : A_next)
+ *   value_targets[t][p] = A + (double)v
+ * The two `done ? 0.0 : x` are selects, so a non-finite value behind a done
+ * does not reach any output. Then advantages = (A - mean) / (std + 1e-12)
+ * with the mean and the unbiased std over all T*P raw advantages, by the
+ * fixed-order two-pass reductions of marlnav_discounted_returns;
+ * value_targets stay in reward units (not normalised).
+ *   rewards, values (T, P) fp32; done (T, P) uint8, the merged terminated |
+ *   truncated flag of the rollout: a truncated episode counts as ended and
+ *   gets no bootstrap (its final observation is overwritten by the in-kernel
+ *   re-init); last_values (P,) fp32, the critic's value of the observation
+ *   after step T-1; advantages, value_targets (T, P) fp64 out; stats: 2 fp64
+ *   out (mean, std of the raw advantages); work:
+ *   marlnav_gae_work_size(P) fp64.
+ * Everything is validated before the first launch (MARLNAV_EINVAL, the
+ * message names the field): NULL pointers, T >= 1, T*P >= 2, gamma and lam
+ * finite and in [0, 1]. No synchronisation, no atomics: equal inputs give
+ * equal bits. */
+int64_t marlnav_gae_work_size(int64_t num_parallel);
+int marlnav_gae_advantages(const float *rewards, const uint8_t *done, const float *values,
+                           const float *last_values, int64_t T, int64_t P, double gamma,
+                           double lam, double *advantages, double *value_targets, double *stats,
+                           double *work, void *stream);
+
 /* Shapes of one policy call. D is the env's observation row length,
  * D = 2 + 2*O + 2*(A-1) for an observed obstacle count O in [1, 256]; H is
  * the hidden size of both networks (models.py:69-70, `hidden_size`). */
@@ -248,6 +278,16 @@ typedef struct MarlnavPolicyBuffers {
  * step_idx are not used. */
 int marlnav_policy_act(const MarlnavPolicyDims *dims, const MarlnavPolicyBuffers *bufs,
                        uint64_t policy_seed, uint64_t step_idx, void *stream);
+
+/* The critic half of marlnav_policy_act alone: Critic.forward (models.py:
+ * 51-56) of (P, A, D) normalised observations into values (P, 1), bit-identical
+ * to the values marlnav_policy_act writes for the same observations and
+ * weights (the bootstrap value of marlnav_gae_advantages). One launch. Reads
+ * obs_norm and the four critic tensors (live); the six actor pointers, eps,
+ * actions, log_probs and eps_out are ignored and may be NULL. Draws no random
+ * number. */
+int marlnav_critic_values(const MarlnavPolicyDims *dims, const MarlnavPolicyBuffers *bufs,
+                          void *stream);
 
 /* Device pointers of one rollout of T steps of P envs: the stacked storage of
  * the six entries MAPPO.get_data keeps per step (models.py:120), row t of each
@@ -567,6 +607,38 @@ int marlnav_ppo_train_phase(int network, const MarlnavPpoDims *dims,
                             int64_t num_batches, int64_t num_epochs, double epsilon,
                             double ent_const, const MarlnavAdamDims *adam_dims,
                             const MarlnavAdamBuffers *adam_bufs, double *loss_log, void *stream);
+
+/* The three actor-side calls above with the pairing of advantages to agent
+ * rows as an argument.
+ *   MARLNAV_ADVANTAGE_REFERENCE  the advantage of agent row i is
+ *     returns[i mod N] - values[i mod N]: each call stores exactly what its
+ *     counterpart without `_mode` stores.
+ *   MARLNAV_ADVANTAGE_ENV  the advantage of agent row i is returns[i / A], the
+ *     row's own (t, p), read as a ready fp64 advantage (the normalised
+ *     `advantages` of marlnav_gae_advantages). `values` is not read by the
+ *     actor and may be NULL. Everything else about the loss and the gradients
+ *     is unchanged, and so are the folded-Adam variants and their two limits.
+ * The critic has no pairing: marlnav_ppo_train_phase_mode with
+ * MARLNAV_NETWORK_CRITIC validates advantage_mode and is otherwise
+ * marlnav_ppo_train_phase (in the GAE mode its `returns` pointer addresses
+ * the value_targets). Any other advantage_mode is MARLNAV_EINVAL before any
+ * launch. */
+#define MARLNAV_ADVANTAGE_REFERENCE 0
+#define MARLNAV_ADVANTAGE_ENV 1
+int marlnav_ppo_actor_grad_mode(const MarlnavPpoDims *dims, const MarlnavPpoBuffers *bufs,
+                                double epsilon, double ent_const, int advantage_mode,
+                                void *stream);
+int marlnav_ppo_actor_update_mode(const MarlnavPpoDims *dims, const MarlnavPpoBuffers *bufs,
+                                  double epsilon, double ent_const,
+                                  const MarlnavAdamDims *adam_dims,
+                                  const MarlnavAdamBuffers *adam_bufs, int advantage_mode,
+                                  void *stream);
+int marlnav_ppo_train_phase_mode(int network, const MarlnavPpoDims *dims,
+                                 const MarlnavPpoBuffers *bufs, const int64_t *bounds,
+                                 int64_t num_batches, int64_t num_epochs, double epsilon,
+                                 double ent_const, const MarlnavAdamDims *adam_dims,
+                                 const MarlnavAdamBuffers *adam_bufs, double *loss_log,
+                                 int advantage_mode, void *stream);
 
 /* fp64 elements of `work` that cover the largest minibatch of the list;
  * negative on bad dims or bounds. */

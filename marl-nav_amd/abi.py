@@ -165,6 +165,9 @@ class MarlnavAdamBuffers(ctypes.Structure):
 
 
 NETWORK_ACTOR, NETWORK_CRITIC = 0, 1
+ADVANTAGE_REFERENCE, ADVANTAGE_ENV = 0, 1
+# what marlnav_critic_values dereferences
+CRITIC_VALUES_REQUIRED = ("obs_norm",) + POLICY_WEIGHT_FIELDS[6:] + ("values",)
 SNAPSHOT_MAX_TENSORS = 10
 
 EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_formation_obs",
@@ -176,6 +179,9 @@ EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_for
            "marlnav_ppo_actor_update", "marlnav_ppo_critic_update",
            "marlnav_ppo_train_phase", "marlnav_ppo_train_work_size",
            "marlnav_params_snapshot_if",
+           "marlnav_gae_work_size", "marlnav_gae_advantages", "marlnav_critic_values",
+           "marlnav_ppo_actor_grad_mode", "marlnav_ppo_actor_update_mode",
+           "marlnav_ppo_train_phase_mode",
            "marlnav_last_error", "marlnav_abi_version",
            "marlnav_debug_force_family", "marlnav_debug_last_family",
            "marlnav_debug_acos_range", "marlnav_debug_fastdiv_check")
@@ -253,6 +259,24 @@ def _declare(lib):
     lib.marlnav_params_snapshot_if.argtypes = [c.c_int, c.POINTER(_P), c.POINTER(_P), i64_p, _P, _P,
                                                _P, c.c_int64, c.c_int, _P]
     lib.marlnav_params_snapshot_if.restype = c.c_int
+    lib.marlnav_gae_work_size.argtypes = [c.c_int64]
+    lib.marlnav_gae_work_size.restype = c.c_int64
+    lib.marlnav_gae_advantages.argtypes = [_P, _P, _P, _P, c.c_int64, c.c_int64, c.c_double,
+                                           c.c_double, _P, _P, _P, _P, _P]
+    lib.marlnav_gae_advantages.restype = c.c_int
+    lib.marlnav_critic_values.argtypes = [c.POINTER(MarlnavPolicyDims),
+                                          c.POINTER(MarlnavPolicyBuffers), _P]
+    lib.marlnav_critic_values.restype = c.c_int
+    lib.marlnav_ppo_actor_grad_mode.argtypes = [ppo_dims_p, ppo_bufs_p, c.c_double, c.c_double,
+                                                c.c_int, _P]
+    lib.marlnav_ppo_actor_grad_mode.restype = c.c_int
+    lib.marlnav_ppo_actor_update_mode.argtypes = [ppo_dims_p, ppo_bufs_p, c.c_double, c.c_double,
+                                                  adam_dims_p, adam_bufs_p, c.c_int, _P]
+    lib.marlnav_ppo_actor_update_mode.restype = c.c_int
+    lib.marlnav_ppo_train_phase_mode.argtypes = [c.c_int, ppo_dims_p, ppo_bufs_p, i64_p, c.c_int64,
+                                                 c.c_int64, c.c_double, c.c_double, adam_dims_p,
+                                                 adam_bufs_p, _P, c.c_int, _P]
+    lib.marlnav_ppo_train_phase_mode.restype = c.c_int
     lib.marlnav_last_error.argtypes = []
     lib.marlnav_last_error.restype = c.c_char_p
     lib.marlnav_abi_version.argtypes = []

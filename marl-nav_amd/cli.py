@@ -23,6 +23,11 @@ num_parallel)`` repeats of rollout, actor phase and critic phase, then the
 reference's weight files, CSVs, params file and figures, and one JSON line.
 
     python -m marlnav_amd --train -np 4096 -bl 16 -bs 8 -ne 4 -nt 1048576
+
+``--gae-lambda L`` with ``--train`` selects the GAE(lambda) advantage mode
+ instead of the reference's normalised returns.
+
+    python -m marlnav_amd --train --gae-lambda 0.95 -np 4096 -bl 16 -bs 8 -ne 4 -nt 1048576
 """
 import argparse
 import sys
@@ -96,6 +101,9 @@ def build_parser():
            'last repeat\'s training, which is the default here too)')
     a('--save-every', type=int, default=0, metavar='N',
       help='with --train: also write the weight files after every N repeats')
+    a('--gae-lambda', type=float, default=None, metavar='LAMBDA',
+      help='with --train: GAE(lambda) advantages in [0, 1] with own-env pairing, the terminal '
+           'reward kept and a bootstrap value (default: the reference\'s normalised returns)')
     a('--out-dir', default='.', help='with --train: where weights/, logs/ and plots/ go')
     a('--plot-dir', default='plots', help='directory of the saved figures')
     a('--no-plots', action='store_true', help='skip the figures, print the series')
@@ -197,6 +205,8 @@ def _train(pkg, args):
     if args.seed is not None:
         pkg.set_all_seeds(args.seed)
     try:
+        if args.gae_lambda is not None:
+            pkg.rollout._check_lambda(args.gae_lambda)
         model_params = pkg.set_model_params(args, device)
     except ValueError as e:
         print(f"--train: {e}", file=sys.stderr)

@@ -29,7 +29,9 @@
 // the Adam step to marlnav_ppo.hip's finish kernels (adam_element.h is the
 // shared element update) where that is faster and enqueue the two launches
 // above elsewhere; and marlnav_params_snapshot_if, the reference's checkpoint
-// rule as a copy launch and one bookkeeping thread.
+// rule as a copy launch and one bookkeeping thread. The `_mode` forms of the
+// actor's calls carry the pairing of advantages to agent rows;
+// the forms without it are calls of them with MARLNAV_ADVANTAGE_REFERENCE.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -273,10 +275,11 @@ extern "C" int marlnav_adam_step(const MarlnavAdamDims *d, const MarlnavAdamBuff
     return enqueue_adam(d, b, (hipStream_t)stream);
 }
 
-extern "C" int marlnav_ppo_actor_update(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
-                                        double epsilon, double ent_const,
-                                        const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
-                                        void *stream)
+extern "C" int marlnav_ppo_actor_update_mode(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                                             double epsilon, double ent_const,
+                                             const MarlnavAdamDims *ad,
+                                             const MarlnavAdamBuffers *ab, int advantage_mode,
+                                             void *stream)
 {
     // every check of both halves before the first launch: the ppo dims
     // (marlnav_ppo_work_size runs them), the Adam arguments, the table; the
@@ -295,9 +298,18 @@ extern "C" int marlnav_ppo_actor_update(const MarlnavPpoDims *d, const MarlnavPp
                                  "actor_mu_b",  "actor_std_w", "actor_std_b"};
     rc = check_table("actor", 6, w, gw, size, name, ad, ab);
     if (rc) return rc;
-    rc = marlnav_ppo_actor_grad(d, b, epsilon, ent_const, stream);
+    rc = marlnav_ppo_actor_grad_mode(d, b, epsilon, ent_const, advantage_mode, stream);
     if (rc) return rc;
     return enqueue_adam(ad, ab, (hipStream_t)stream);
+}
+
+extern "C" int marlnav_ppo_actor_update(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                                        double epsilon, double ent_const,
+                                        const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
+                                        void *stream)
+{
+    return marlnav_ppo_actor_update_mode(d, b, epsilon, ent_const, ad, ab,
+                                         MARLNAV_ADVANTAGE_REFERENCE, stream);
 }
 
 extern "C" int marlnav_ppo_critic_update(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
@@ -326,8 +338,8 @@ extern "C" int marlnav_ppo_critic_update(const MarlnavPpoDims *d, const MarlnavP
 // =========================================================================
 __attribute__((visibility("hidden"))) int marlnav_internal_ppo_fold(
     int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
-    double ent_const, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, void *stream,
-    int check_only);
+    double ent_const, int advantage_mode, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
+    void *stream, int check_only);
 
 namespace {
 
@@ -368,7 +380,7 @@ void minibatch(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, int64_t lo, 
     mb->obs = b->obs + arows * d->obs_dim;
     if (b->actions) mb->actions = b->actions + arows * 2;
     if (b->log_probs) mb->log_probs = b->log_probs + arows;
-    mb->values = b->values + rows;
+    if (b->values) mb->values = b->values + rows;
     mb->returns = b->returns + rows;
     mb->loss = loss;
 }
@@ -392,17 +404,24 @@ extern "C" int64_t marlnav_ppo_train_work_size(const MarlnavPpoDims *d, const in
     return need;
 }
 
-extern "C" int marlnav_ppo_train_phase(int network, const MarlnavPpoDims *d,
-                                       const MarlnavPpoBuffers *b, const int64_t *bounds,
-                                       int64_t num_batches, int64_t num_epochs, double epsilon,
-                                       double ent_const, const MarlnavAdamDims *ad,
-                                       const MarlnavAdamBuffers *ab, double *loss_log,
-                                       void *stream)
+extern "C" int marlnav_ppo_train_phase_mode(int network, const MarlnavPpoDims *d,
+                                            const MarlnavPpoBuffers *b, const int64_t *bounds,
+                                            int64_t num_batches, int64_t num_epochs,
+                                            double epsilon, double ent_const,
+                                            const MarlnavAdamDims *ad,
+                                            const MarlnavAdamBuffers *ab, double *loss_log,
+                                            int advantage_mode, void *stream)
 {
     // ---- every check before the first launch
     if (network != MARLNAV_NETWORK_ACTOR && network != MARLNAV_NETWORK_CRITIC)
         return fail_ll("train: network=%lld must be MARLNAV_NETWORK_ACTOR or _CRITIC", network, 0,
                        0);
+    if (advantage_mode != MARLNAV_ADVANTAGE_REFERENCE && advantage_mode != MARLNAV_ADVANTAGE_ENV)
+        return fail_ll("train: advantage_mode=%lld must be MARLNAV_ADVANTAGE_REFERENCE or _ENV",
+                       advantage_mode, 0, 0);
+    // the own-env pairing is the actor's: it reads no values
+    const bool need_values =
+        network == MARLNAV_NETWORK_CRITIC || advantage_mode == MARLNAV_ADVANTAGE_REFERENCE;
     if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
     if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
     if (num_epochs < 1) return fail_ll("train: num_epochs=%lld < 1", num_epochs, 0, 0);
@@ -435,13 +454,15 @@ extern "C" int marlnav_ppo_train_phase(int network, const MarlnavPpoDims *d,
     }
     if (rc) return rc;
     if (!b->obs) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer obs is NULL");
-    if (!b->values) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer values is NULL");
+    if (need_values && !b->values)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer values is NULL");
     if (!b->returns) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer returns is NULL");
     MarlnavPpoDims md;
     MarlnavPpoBuffers mb;
     for (int64_t j = 0; j < num_batches; ++j) {  // dims and buffers of every minibatch
         minibatch(d, b, bounds[2 * j], bounds[2 * j + 1], loss_log, &md, &mb);
-        rc = marlnav_internal_ppo_fold(network, &md, &mb, epsilon, ent_const, ad, ab, stream, 1);
+        rc = marlnav_internal_ppo_fold(network, &md, &mb, epsilon, ent_const, advantage_mode, ad,
+                                       ab, stream, 1);
         if (rc) return rc;
     }
     // ---- num_epochs x num_batches updates, epoch-major: two launches for the
@@ -451,12 +472,24 @@ extern "C" int marlnav_ppo_train_phase(int network, const MarlnavPpoDims *d,
     for (int64_t e = 0; e < num_epochs; ++e)
         for (int64_t j = 0; j < num_batches; ++j, ++k) {
             minibatch(d, b, bounds[2 * j], bounds[2 * j + 1], loss_log + k, &md, &mb);
-            rc = marlnav_internal_ppo_fold(network, &md, &mb, epsilon, ent_const, ad, ab, stream,
-                                           0);
+            rc = marlnav_internal_ppo_fold(network, &md, &mb, epsilon, ent_const, advantage_mode,
+                                           ad, ab, stream, 0);
             if (rc == 1) rc = enqueue_adam(ad, ab, (hipStream_t)stream);  // not folded
             if (rc) return rc;
         }
     return 0;
+}
+
+extern "C" int marlnav_ppo_train_phase(int network, const MarlnavPpoDims *d,
+                                       const MarlnavPpoBuffers *b, const int64_t *bounds,
+                                       int64_t num_batches, int64_t num_epochs, double epsilon,
+                                       double ent_const, const MarlnavAdamDims *ad,
+                                       const MarlnavAdamBuffers *ab, double *loss_log,
+                                       void *stream)
+{
+    return marlnav_ppo_train_phase_mode(network, d, b, bounds, num_batches, num_epochs, epsilon,
+                                        ent_const, ad, ab, loss_log, MARLNAV_ADVANTAGE_REFERENCE,
+                                        stream);
 }
 
 // =========================================================================

@@ -320,6 +320,86 @@ __global__ void __launch_bounds__(kThreads) policy_kernel(PolicyArgs g)
     }
 }
 
+// The critic of policy_kernel alone (marlnav_critic_values):
+// the same blocks of 64 envs, the same wave shares of the hidden units, the
+// same FMA chains and the same wave-order sum, so values[env] carries the bits
+// policy_kernel stores for the same observations and weights. It is a kernel
+// of its own, not a mode of policy_kernel, and the critic sum is restated, not
+// shared: a function called from both changed policy_kernel's compiled code,
+// and the rollout's hot launch keeps its code. The bit
+// identity is held by tests/test_gae_gpu.py. Reads no actor tensor and draws
+// nothing.
+template <int A_T, int D_T>
+__global__ void __launch_bounds__(kThreads) critic_values_kernel(PolicyArgs g)
+{
+    const int AD = (A_T ? A_T : g.A) * (D_T ? D_T : g.D);
+    const int H = g.H;
+    const int64_t P = g.P;
+    __shared__ float s_part[kWaves * kEnvsPerBlock];
+
+    const int t = threadIdx.x;
+    const int q = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int e = t & 63;
+    const int Hq = (H + kWaves - 1) / kWaves;
+    const int j0 = q * Hq, j1 = (j0 + Hq < H) ? j0 + Hq : H;
+
+    const int64_t env_raw = (int64_t)blockIdx.x * kEnvsPerBlock + e;
+    const int64_t env = env_raw < P ? env_raw : P - 1;  // lanes past the end stay in bounds
+    const float *__restrict__ xe = g.b.obs_norm + env * AD;
+    const float *__restrict__ wc = g.b.critic_fc1_w;
+    const float *__restrict__ bc = g.b.critic_fc1_b;
+    const float *__restrict__ w2 = g.b.critic_fc2_w;
+    float part = 0.0f;
+    if constexpr (A_T != 0 && D_T != 0) {
+        float x[A_T * D_T];
+        load_row<A_T * D_T>(xe, x);
+        for (int j = j0; j < j1; j += 4) {
+            float acc[4];
+            const float *wr[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int jj = j + i < j1 ? j + i : j1 - 1;  // a short last group repeats a row
+                acc[i] = bc[jj];
+                wr[i] = wc + (int64_t)jj * (A_T * D_T);
+            }
+#pragma unroll
+            for (int k = 0; k < A_T * D_T; ++k)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[i] = __builtin_fmaf(wr[i][k], x[k], acc[i]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (j + i < j1) part = __builtin_fmaf(w2[j + i], relu_t(acc[i]), part);
+        }
+    } else {
+        for (int j = j0; j < j1; j += 4) {
+            float acc[4];
+            const float *wr[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int jj = j + i < j1 ? j + i : j1 - 1;
+                acc[i] = bc[jj];
+                wr[i] = wc + (int64_t)jj * AD;
+            }
+            for (int k = 0; k < AD; ++k) {
+                const float xv = xe[k];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[i] = __builtin_fmaf(wr[i][k], xv, acc[i]);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (j + i < j1) part = __builtin_fmaf(w2[j + i], relu_t(acc[i]), part);
+        }
+    }
+    s_part[q * kEnvsPerBlock + e] = part;
+    __syncthreads();
+    if (t < kEnvsPerBlock && env_raw < P) {
+        float v = s_part[t];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) v += s_part[w * kEnvsPerBlock + t];
+        g.b.values[env_raw] = v + g.b.critic_fc2_b[0];
+    }
+}
+
 using PolicyFn = void (*)(PolicyArgs);
 
 struct PolicyVariant {
@@ -332,6 +412,10 @@ const PolicyVariant kVariants[] = {
     {3, 12, policy_kernel<3, 12>},
     {3, 22, policy_kernel<3, 22>},
 };
+const PolicyVariant kCriticVariants[] = {
+    {3, 12, critic_values_kernel<3, 12>},
+    {3, 22, critic_values_kernel<3, 22>},
+};
 
 int failf(int code, const char *fmt, long long a, long long b, long long c)
 {
@@ -340,10 +424,8 @@ int failf(int code, const char *fmt, long long a, long long b, long long c)
     return marlnav_internal_fail(code, msg);
 }
 
-}  // namespace
-
-extern "C" int marlnav_policy_act(const MarlnavPolicyDims *d, const MarlnavPolicyBuffers *b,
-                                  uint64_t policy_seed, uint64_t step_idx, void *stream)
+// the dims checks of both entry points; 0 or the failing code
+int check_dims(const MarlnavPolicyDims *d, const MarlnavPolicyBuffers *b)
 {
     if (!d || !b) return marlnav_internal_fail(MARLNAV_EINVAL, "policy dims/buffers is NULL");
     if (d->num_parallel < 1)
@@ -366,6 +448,15 @@ extern "C" int marlnav_policy_act(const MarlnavPolicyDims *d, const MarlnavPolic
     if (d->reserved != 0 || d->env_offset < 0)
         return failf(MARLNAV_EINVAL, "policy: reserved=%lld must be 0 and env_offset=%lld >= 0",
                      d->reserved, d->env_offset, 0);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int marlnav_policy_act(const MarlnavPolicyDims *d, const MarlnavPolicyBuffers *b,
+                                  uint64_t policy_seed, uint64_t step_idx, void *stream)
+{
+    if (int rc = check_dims(d, b)) return rc;
     if (!b->obs_norm || !b->actor_fc1_w || !b->actor_fc1_b || !b->actor_mu_w || !b->actor_mu_b ||
         !b->actor_std_w || !b->actor_std_b || !b->critic_fc1_w || !b->critic_fc1_b ||
         !b->critic_fc2_w || !b->critic_fc2_b || !b->actions || !b->log_probs || !b->values)
@@ -390,6 +481,37 @@ extern "C" int marlnav_policy_act(const MarlnavPolicyDims *d, const MarlnavPolic
             if (v.A == args.A && v.D == args.D) fn = v.fn;
     const size_t lds = sizeof(float) * lds_floats(args.D);
     hipLaunchKernelGGL(fn, dim3((unsigned)nblk), dim3(kThreads), lds, (hipStream_t)stream, args);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int marlnav_critic_values(const MarlnavPolicyDims *d, const MarlnavPolicyBuffers *b,
+                                     void *stream)
+{
+    if (int rc = check_dims(d, b)) return rc;
+    if (!b->obs_norm || !b->critic_fc1_w || !b->critic_fc1_b || !b->critic_fc2_w ||
+        !b->critic_fc2_b || !b->values)
+        return marlnav_internal_fail(
+            MARLNAV_EINVAL, "critic values: a required buffer (obs_norm, critic_*, values) is NULL");
+    const int64_t nblk = (d->num_parallel + kEnvsPerBlock - 1) / kEnvsPerBlock;
+    if (nblk > 0x7fffffff)
+        return failf(MARLNAV_EINVAL, "policy: num_parallel=%lld too large", d->num_parallel, 0, 0);
+
+    PolicyArgs args;
+    args.b = *b;
+    args.P = d->num_parallel;
+    args.env_offset = d->env_offset;
+    args.A = d->num_agents;
+    args.D = d->obs_dim;
+    args.H = d->hidden_size;
+    args.seed = 0;
+    args.step = 0;
+    PolicyFn fn = critic_values_kernel<0, 0>;
+    if ((reinterpret_cast<uintptr_t>(b->obs_norm) & 15u) == 0)
+        for (const PolicyVariant &v : kCriticVariants)
+            if (v.A == args.A && v.D == args.D) fn = v.fn;
+    hipLaunchKernelGGL(fn, dim3((unsigned)nblk), dim3(kThreads), 0, (hipStream_t)stream, args);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
     return 0;

@@ -198,7 +198,14 @@ static_assert(actor_lds_bytes(kMaxD) <= 64 * 1024, "LDS of the widest row");
 // ones column), then the surrogate sum and the entropy sum
 __device__ __host__ inline int64_t actor_stride(int D) { return 4 * (int64_t)(D + 1) + 2; }
 
-template <class... X>
+//
+// PAIRING: which entry of the (t, p) vectors is the advantage of agent row i.
+// kPairReference: returns[i mod N] - values[i mod N], the reference's
+// repeat(num_agents). kPairEnv: returns[i / A], the row's own
+// env, read as a ready fp64 advantage; values is not read.
+enum { kPairReference = 0, kPairEnv = 1 };
+
+template <int PAIRING, class... X>
 __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
 {
     const int D = g.D, H = g.H;
@@ -263,7 +270,9 @@ __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
     for (int64_t tile = row_lo; tile < row_hi; tile += kActorTile) {
         // ---- phase 1: thread = row
         const int64_t row = tile + t;
-        const int64_t tile_n = tile % N;  // wave-uniform: one scalar division per tile
+        // wave-uniform: one scalar division per tile
+        const int64_t tile_n = PAIRING == kPairEnv ? tile / g.A : tile % N;
+        const int tile_a = PAIRING == kPairEnv ? (int)(tile - tile_n * g.A) : 0;
         float4 gr4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (row < row_hi) {
             const float *__restrict__ xr = g.b.obs + row * D;
@@ -288,10 +297,16 @@ __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
             const float lp = __builtin_fmaf(-0.5f, q0 + q1, __builtin_fmaf(-0.5f, ld, -kLog2Pi));
             const float ent = __builtin_fmaf(0.5f, ld, 1.0f + kLog2Pi);
             const float ratio = expf(lp - g.b.log_probs[row]);
-            // row mod N: the reference's repeat(num_agents), not the row's env
-            int64_t n = tile_n + t;
-            if (n >= N) n = N >= kActorTile ? n - N : n % N;
-            const double adv = g.b.returns[n] - (double)g.b.values[n];
+            double adv;
+            if constexpr (PAIRING == kPairEnv) {
+                // row / A: the row's own env row, tile = tile_n A + tile_a
+                adv = g.b.returns[tile_n + (tile_a + t) / g.A];
+            } else {
+                // row mod N: the reference's repeat(num_agents), not the row's env
+                int64_t n = tile_n + t;
+                if (n >= N) n = N >= kActorTile ? n - N : n % N;
+                adv = g.b.returns[n] - (double)g.b.values[n];
+            }
             const float rc = ratio < g.clip_lo ? g.clip_lo : (ratio > g.clip_hi ? g.clip_hi : ratio);
             const double sa = (double)ratio * adv, sb = (double)rc * adv;
             sum_surr += sb < sa ? sb : sa;
@@ -931,13 +946,23 @@ extern "C" int64_t marlnav_ppo_work_size(const MarlnavPpoDims *d)
 
 namespace {
 
-int check_actor_bufs(const MarlnavPpoBuffers *b)
+int check_mode(int advantage_mode)
+{
+    if (advantage_mode != MARLNAV_ADVANTAGE_REFERENCE && advantage_mode != MARLNAV_ADVANTAGE_ENV)
+        return failf(MARLNAV_EINVAL,
+                     "ppo: advantage_mode=%lld must be MARLNAV_ADVANTAGE_REFERENCE or _ENV",
+                     advantage_mode, 0, 0);
+    return 0;
+}
+
+// values is read by the reference pairing only
+int check_actor_bufs(const MarlnavPpoBuffers *b, int advantage_mode)
 {
     if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
     PPO_NEED(obs);
     PPO_NEED(actions);
     PPO_NEED(log_probs);
-    PPO_NEED(values);
+    if (advantage_mode == MARLNAV_ADVANTAGE_REFERENCE) PPO_NEED(values);
     PPO_NEED(returns);
     PPO_NEED(actor_fc1_w);
     PPO_NEED(actor_fc1_b);
@@ -987,7 +1012,8 @@ int launch_status()
 // checked arguments only. adv / fold NULL: the two launches of
 // marlnav_ppo_actor_grad; given: the same two with the Adam step folded in.
 int enqueue_actor(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
-                  double ent_const, const AdvArgs *adv, const FoldArgs *fold, hipStream_t s)
+                  double ent_const, int advantage_mode, const AdvArgs *adv, const FoldArgs *fold,
+                  hipStream_t s)
 {
     PpoArgs a = make_args(d, b);
     actor_grid(a.M, a.rows_per_block, a.nblocks);
@@ -999,13 +1025,20 @@ int enqueue_actor(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double ep
     const int nS = 4 * (a.D + 1) + 2;
     const int groups = nS >= kThreads ? 1 : kThreads / nS;
     const size_t fin_lds = sizeof(double) * (size_t)nS * (1 + (groups > 1 ? groups : 0));
+    const dim3 grid((unsigned)a.nblocks), blk(kThreads);
+    const size_t lds = actor_lds_bytes(a.D);
+    const bool env = advantage_mode == MARLNAV_ADVANTAGE_ENV;
     if (fold) {
-        hipLaunchKernelGGL(actor_pass, dim3((unsigned)a.nblocks), dim3(kThreads),
-                           actor_lds_bytes(a.D), s, a, *adv);
+        if (env)
+            hipLaunchKernelGGL((actor_pass<kPairEnv>), grid, blk, lds, s, a, *adv);
+        else
+            hipLaunchKernelGGL((actor_pass<kPairReference>), grid, blk, lds, s, a, *adv);
         hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), fin_lds, s, a, *fold);
     } else {
-        hipLaunchKernelGGL(actor_pass, dim3((unsigned)a.nblocks), dim3(kThreads),
-                           actor_lds_bytes(a.D), s, a);
+        if (env)
+            hipLaunchKernelGGL((actor_pass<kPairEnv>), grid, blk, lds, s, a);
+        else
+            hipLaunchKernelGGL((actor_pass<kPairReference>), grid, blk, lds, s, a);
         hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), fin_lds, s, a);
     }
     return launch_status();
@@ -1073,14 +1106,25 @@ int enqueue_critic(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double e
 
 }  // namespace
 
-extern "C" int marlnav_ppo_actor_grad(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
-                                      double epsilon, double ent_const, void *stream)
+extern "C" int marlnav_ppo_actor_grad_mode(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                                           double epsilon, double ent_const, int advantage_mode,
+                                           void *stream)
 {
     int rc = check_dims(d);
     if (rc) return rc;
-    rc = check_actor_bufs(b);
+    rc = check_mode(advantage_mode);
     if (rc) return rc;
-    return enqueue_actor(d, b, epsilon, ent_const, nullptr, nullptr, (hipStream_t)stream);
+    rc = check_actor_bufs(b, advantage_mode);
+    if (rc) return rc;
+    return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
+                         (hipStream_t)stream);
+}
+
+extern "C" int marlnav_ppo_actor_grad(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                                      double epsilon, double ent_const, void *stream)
+{
+    return marlnav_ppo_actor_grad_mode(d, b, epsilon, ent_const, MARLNAV_ADVANTAGE_REFERENCE,
+                                       stream);
 }
 
 extern "C" int marlnav_ppo_critic_grad(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
@@ -1108,23 +1152,25 @@ constexpr int64_t kCriticFoldMaxRows = (int64_t)1 << 17;
 
 // One minibatch update for marlnav_ppo_train_phase (marlnav_adam.hip), which
 // has checked the Adam arguments and that the table is this network's own.
-// network 0: the actor, 1: the critic. check_only: the dims and buffer checks
-// of this update and nothing launched. Returns 0 with the Adam step folded
+// network 0: the actor, 1: the critic (advantage_mode, checked by the caller,
+// is the actor's). check_only: the dims and buffer checks of this update and
+// nothing launched. Returns 0 with the Adam step folded
 // into the finish launch, 1 with the gradient launches alone enqueued (the
 // caller then enqueues the Adam step), negative on an error.
 __attribute__((visibility("hidden"))) int marlnav_internal_ppo_fold(
     int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
-    double ent_const, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, void *stream,
-    int check_only)
+    double ent_const, int advantage_mode, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
+    void *stream, int check_only)
 {
     int rc = check_dims(d);
     if (rc) return rc;
-    rc = network == 0 ? check_actor_bufs(b) : check_critic_bufs(b);
+    rc = network == 0 ? check_actor_bufs(b, advantage_mode) : check_critic_bufs(b);
     if (rc || check_only) return rc;
     if (network == 0) {
         const int64_t H = d->hidden_size, D = d->obs_dim;
         if (H * (D + 1) + 4 * H + 4 > kActorFoldMaxElements) {
-            rc = enqueue_actor(d, b, epsilon, ent_const, nullptr, nullptr, (hipStream_t)stream);
+            rc = enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
+                               (hipStream_t)stream);
             return rc ? rc : 1;
         }
     } else if (d->num_steps * d->num_parallel > kCriticFoldMaxRows) {
@@ -1151,6 +1197,7 @@ __attribute__((visibility("hidden"))) int marlnav_internal_ppo_fold(
     f.eps = ad->eps;
     f.maximize = ad->maximize;
     if (network == 0)
-        return enqueue_actor(d, b, epsilon, ent_const, &adv, &f, (hipStream_t)stream);
+        return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, &adv, &f,
+                             (hipStream_t)stream);
     return enqueue_critic(d, b, epsilon, &adv, &f, (hipStream_t)stream);
 }

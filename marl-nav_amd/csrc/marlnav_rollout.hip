@@ -8,6 +8,10 @@
 // and unbiased std are two-pass block reductions in a fixed order, so results
 // are deterministic run to run.
 //
+// marlnav_gae_advantages: the GAE(lambda) scan of the opt-in advantage mode
+// (DESIGN.md §15), the same one-thread-per-env backward walk with the critic's
+// values and a bootstrap value beside the rewards, and the same reductions.
+//
 // marlnav_rollout_collect: the whole of MAPPO.get_data (models.py:106-125) as
 // one host call that enqueues the existing observe / policy / step launches
 // back to back, each step kernel writing its normalised observations straight
@@ -59,6 +63,44 @@ __global__ void __launch_bounds__(kThreads) returns_kernel(const float *__restri
             g = done[i] ? 0.0 : (double)rew[i] + gamma * g;
             ret[i] = g;
             s += g;
+        }
+    }
+    const double b = block_sum(s, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = b;
+}
+
+// GAE(lambda): one thread per env walks its column backwards
+// in fp64, as returns_kernel does. Selects, not products with a mask, so a
+// non-finite value behind a done cannot leak. gl = gamma * lambda (host, fp64).
+//   next  = t == T-1 ? last[p] : val[t+1][p]
+//   delta = (r + gamma * (done ? 0 : next)) - v
+//   A     = delta + gl * (done ? 0 : A_next)
+//   vt    = A + v
+__global__ void __launch_bounds__(kThreads) gae_kernel(const float *__restrict__ rew,
+                                                        const uint8_t *__restrict__ done,
+                                                        const float *__restrict__ val,
+                                                        const float *__restrict__ last, int64_t T,
+                                                        int64_t P, double gamma, double gl,
+                                                        double *__restrict__ adv,
+                                                        double *__restrict__ vt,
+                                                        double *__restrict__ partial)
+{
+    __shared__ double sh[kThreads / 64];
+    const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    double s = 0.0;
+    if (e < P) {
+        double a = 0.0;
+        double next = (double)last[e];
+        for (int64_t t = T - 1; t >= 0; --t) {
+            const int64_t i = t * P + e;
+            const bool d = done[i] != 0;
+            const double v = (double)val[i];
+            const double delta = ((double)rew[i] + gamma * (d ? 0.0 : next)) - v;
+            a = delta + gl * (d ? 0.0 : a);
+            adv[i] = a;
+            vt[i] = a + v;
+            s += a;
+            next = v;
         }
     }
     const double b = block_sum(s, sh);
@@ -218,6 +260,58 @@ int marlnav_discounted_returns(const float *rewards, const uint8_t *done, int64_
     hipLaunchKernelGGL(sqdev_kernel, grid, blk, 0, s, returns, T, P, stats, work + nb);
     hipLaunchKernelGGL(finish_kernel, dim3(1), blk, 0, s, work + nb, nb, T * P, 1, stats);
     hipLaunchKernelGGL(normalize_kernel, grid, blk, 0, s, returns, T, P, stats);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
+    return 0;
+}
+
+int64_t marlnav_gae_work_size(int64_t P)
+{
+    return P < 1 ? -1 : 2 * blocks_for(P);
+}
+
+int marlnav_gae_advantages(const float *rewards, const uint8_t *done, const float *values,
+                           const float *last_values, int64_t T, int64_t P, double gamma,
+                           double lam, double *advantages, double *value_targets, double *stats,
+                           double *work, void *stream)
+{
+    // ---- everything is checked before the first launch
+#define MARLNAV_GAE_NEED(f) \
+    if (!f) return failf(MARLNAV_EINVAL, "marlnav_gae_advantages: " #f " is NULL")
+    MARLNAV_GAE_NEED(rewards);
+    MARLNAV_GAE_NEED(done);
+    MARLNAV_GAE_NEED(values);
+    MARLNAV_GAE_NEED(last_values);
+    MARLNAV_GAE_NEED(advantages);
+    MARLNAV_GAE_NEED(value_targets);
+    MARLNAV_GAE_NEED(stats);
+    MARLNAV_GAE_NEED(work);
+#undef MARLNAV_GAE_NEED
+    if (T < 1) return failf(MARLNAV_EINVAL, "marlnav_gae_advantages: T=%lld < 1", (long long)T);
+    if (P < 1) return failf(MARLNAV_EINVAL, "marlnav_gae_advantages: P=%lld < 1", (long long)P);
+    if (T > ((int64_t)1 << 40) / P)
+        return failf(MARLNAV_EINVAL, "marlnav_gae_advantages: T=%lld x P=%lld values are too many",
+                     (long long)T, (long long)P);
+    if (T * P < 2)
+        return failf(MARLNAV_EINVAL, "marlnav_gae_advantages: T=%lld x P=%lld gives fewer than 2 "
+                     "values (the unbiased std needs 2)", (long long)T, (long long)P);
+    if (!(gamma >= 0.0 && gamma <= 1.0))  // a NaN fails both
+        return failf(MARLNAV_EINVAL, "marlnav_gae_advantages: gamma=%g outside [0, 1]", gamma);
+    if (!(lam >= 0.0 && lam <= 1.0))
+        return failf(MARLNAV_EINVAL, "marlnav_gae_advantages: lam=%g outside [0, 1]", lam);
+    const int64_t nb = blocks_for(P);
+    if (nb > 0x7fffffff)
+        return failf(MARLNAV_EINVAL, "marlnav_gae_advantages: P=%lld too large", (long long)P);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)nb), blk(kThreads);
+    const double gl = gamma * lam;
+    hipLaunchKernelGGL(gae_kernel, grid, blk, 0, s, rewards, done, values, last_values, T, P,
+                       gamma, gl, advantages, value_targets, work);
+    // mean, unbiased std and the normalisation: the returns path's launches
+    hipLaunchKernelGGL(finish_kernel, dim3(1), blk, 0, s, work, nb, T * P, 0, stats);
+    hipLaunchKernelGGL(sqdev_kernel, grid, blk, 0, s, advantages, T, P, stats, work + nb);
+    hipLaunchKernelGGL(finish_kernel, dim3(1), blk, 0, s, work + nb, nb, T * P, 1, stats);
+    hipLaunchKernelGGL(normalize_kernel, grid, blk, 0, s, advantages, T, P, stats);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
     return 0;

@@ -17,6 +17,11 @@ as one HIP scan instead of a Python loop of T x 3 small tensor ops.
   ``MultivariateNormal``'s ``sample`` and ``log_prob``, ``Critic.forward``) as
   one launch of libmarlnav.so ``marlnav_policy_act`` on the modules' live
   parameter tensors.
+* ``gae_advantages(rewards, done, values, last_values, gamma, lam)`` - the
+  opt-in GAE(lambda) estimator (libmarlnav.so ``marlnav_gae_advantages``,
+  DESIGN.md §15), ``RolloutBuffer.process_gae``, ``FusedPolicy.values`` (the
+  bootstrap value) and ``FusedPPO(..., advantage='gae')``; ``collect`` /
+  ``collect_fused`` take ``gae_lambda``.
 * ``collect(env, policy, buffer)`` - the ``get_data`` loop (models.py:106-125)
   around ``Env.step`` with no ``torch.nn`` / ``torch.distributions`` call in it.
 * ``collect_fused(env, policy, buffer)`` - the same rollout enqueued by one C
@@ -77,6 +82,42 @@ def discounted_returns(rewards, done, gamma):
     return out, stats[0], stats[1]
 
 
+def gae_advantages(rewards, done, values, last_values, gamma, lam):
+    """GAE(lambda) of a stacked rollout (libmarlnav.so ``marlnav_gae_advantages``,
+    DESIGN.md §15). rewards (T, P) float32, done (T, P) bool (terminated |
+    truncated: a truncated episode counts as ended and gets no bootstrap),
+    values (T, P) or (T, P, 1) float32 as collected, last_values (P,) or
+    (P, 1) float32: the critic's value of the observation after the last step.
+    Returns (advantages (T, P) float64 normalised over all T*P, value_targets
+    (T, P) float64 in reward units, mean and unbiased std of the raw
+    advantages as 0-d float64). Nothing synchronises."""
+    if rewards.dim() != 2 or done.shape != rewards.shape:
+        raise ValueError(f"rewards and done must be (T, P); got {tuple(rewards.shape)}, "
+                         f"{tuple(done.shape)}")
+    dev = rewards.device
+    if dev.type != "cuda":
+        raise RuntimeError("gae_advantages runs on a HIP device (no CPU fallback)")
+    T, P = rewards.shape
+    if values.numel() != T * P or values.shape[:2] != rewards.shape:
+        raise ValueError(f"values must be (T, P) or (T, P, 1); got {tuple(values.shape)}")
+    if last_values.numel() != P:
+        raise ValueError(f"last_values must be (P,) or (P, 1); got {tuple(last_values.shape)}")
+    lib = abi.load_library()
+    rew = rewards.to(torch.float32).contiguous()
+    dn = done.to(device=dev, dtype=torch.bool).contiguous().view(torch.uint8)
+    val = values.to(device=dev, dtype=torch.float32).contiguous()
+    last = last_values.to(device=dev, dtype=torch.float32).contiguous()
+    adv = torch.empty(T, P, dtype=_F64, device=dev)
+    vt = torch.empty(T, P, dtype=_F64, device=dev)
+    stats = torch.empty(2, dtype=_F64, device=dev)
+    work = torch.empty(int(lib.marlnav_gae_work_size(P)), dtype=_F64, device=dev)
+    abi.check(lib.marlnav_gae_advantages(
+        rew.data_ptr(), dn.data_ptr(), val.data_ptr(), last.data_ptr(), T, P,
+        ctypes.c_double(float(gamma)), ctypes.c_double(float(lam)), adv.data_ptr(), vt.data_ptr(),
+        stats.data_ptr(), work.data_ptr(), _stream(dev)), lib)
+    return adv, vt, stats[0], stats[1]
+
+
 def process_rewards(buffer, gamma):
     """models.py:131-148 on the reference's list buffer: every entry's reward
     slot (index -2) becomes its normalized float64 return. Returns the mean
@@ -105,13 +146,14 @@ class RolloutBuffer(object):
     log_probs, values, rewards, done. Storage is allocated on the first
     ``add`` from the shapes and dtypes given."""
 
-    REWARDS, DONE = 4, 5
+    VALUES, REWARDS, DONE = 3, 4, 5
 
     def __init__(self, buffer_len):
         self.buffer_len = int(buffer_len)
         self._store = None
         self._n = 0
         self.returns = None
+        self.advantages = self.value_targets = None    # process_gae
 
     def __len__(self):
         return self._n
@@ -130,6 +172,7 @@ class RolloutBuffer(object):
     def clear(self):
         self._n = 0
         self.returns = None
+        self.advantages = self.value_targets = None
 
     def reserve(self, num_parallel, num_agents, obs_dim, device):
         """Allocate the storage for MAPPO.get_data's entry shapes (models.py:
@@ -163,6 +206,7 @@ class RolloutBuffer(object):
             raise IndexError(f"{n} steps do not fit the rollout buffer ({self.buffer_len})")
         self._n = int(n)
         self.returns = None
+        self.advantages = self.value_targets = None
 
     def stacked(self, k):
         """Entry k (0..5) of every stored step, stacked: (n, ...)."""
@@ -174,6 +218,17 @@ class RolloutBuffer(object):
         ret, mean, _ = discounted_returns(self.stacked(self.REWARDS), self.stacked(self.DONE),
                                           gamma)
         self.returns = ret
+        return mean
+
+    def process_gae(self, gamma, lam, last_values):
+        """``gae_advantages`` over the stored steps with ``last_values`` (P,)
+        or (P, 1), the critic's value of the observation after the last one:
+        sets ``advantages`` (normalised) and ``value_targets`` (reward units),
+        both (n, P) float64; ``returns`` is left alone. Returns the mean of
+        the raw advantages."""
+        adv, vt, mean, _ = gae_advantages(self.stacked(self.REWARDS), self.stacked(self.DONE),
+                                          self.stacked(self.VALUES), last_values, gamma, lam)
+        self.advantages, self.value_targets = adv, vt
         return mean
 
     def entries(self):
@@ -300,8 +355,36 @@ class FusedPolicy(object):
                                                int(step_idx), _stream(self.device)), self._lib)
         return actions, log_probs, values
 
+    def values(self, obs_norm, out=None):
+        """obs_norm (P, A, D) normalised observations -> values (P, 1): the
+        critic alone (libmarlnav.so ``marlnav_critic_values``), bit-identical
+        to ``act(obs_norm, ...)[2]``. Reads no actor weight, draws no random
+        number and leaves ``step_idx`` alone. ``out``: a (P, 1) tensor to write
+        into. One launch on the current stream, no synchronisation."""
+        if obs_norm.dim() != 3:
+            raise ValueError(f"obs_norm must be (P, A, D), got {tuple(obs_norm.shape)}")
+        P, A, D = int(obs_norm.shape[0]), self.num_agents, self.obs_dim
+        b, d = self._bufs, self._dims
+        b.obs_norm = self._check(obs_norm, (P, A, D), "obs_norm")
+        if out is None:
+            out = torch.empty(P, 1, device=self.device)
+        b.values = self._check(out, (P, 1), "out (values)")
+        for f, t in self._params:
+            setattr(b, f, t.data_ptr())
+        d.num_parallel = P
+        abi.check(self._lib.marlnav_critic_values(ctypes.byref(d), ctypes.byref(b),
+                                                  _stream(self.device)), self._lib)
+        return out
 
-def collect(env, policy, buffer, eps_source=None, gamma=0.9):
+
+def _check_lambda(gae_lambda):
+    lam = float(gae_lambda)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"gae_lambda={gae_lambda} must be in [0, 1]")
+    return lam
+
+
+def collect(env, policy, buffer, eps_source=None, gamma=0.9, gae_lambda=None):
     """MAPPO.get_data's loop (models.py:106-125) for ``buffer.buffer_len``
     steps: the initial normalised observations, then per step ``policy.act``
     straight into the buffer's row, ``env.step`` on those actions (the env's
@@ -313,7 +396,13 @@ def collect(env, policy, buffer, eps_source=None, gamma=0.9):
     the caller.
 
     ``eps_source(t)``: the (P*A, 2) standard normals of step ``t`` (None: the
-    kernel's own stream). Returns ``(mean_rew, {'trunc', 'col', 'tar'})``."""
+    kernel's own stream). Returns ``(mean_rew, {'trunc', 'col', 'tar'})``.
+
+    ``gae_lambda`` (None: the reference's estimator alone): also
+    ``policy.values`` of the normalised observations the env holds after the
+    last step and ``buffer.process_gae(gamma, gae_lambda, ...)`` (DESIGN.md
+    §15). The returns and ``mean_rew`` are computed either way."""
+    lam = None if gae_lambda is None else _check_lambda(gae_lambda)
     nrm = env._normalizer
     if nrm is None or env._action_scaler is None:
         raise RuntimeError("collect needs env.attach_normalizer(...) and "
@@ -338,13 +427,15 @@ def collect(env, policy, buffer, eps_source=None, gamma=0.9):
         obs_n = nrm(obs)
     buffer.commit(T)
     mean = buffer.process_rewards(gamma)
+    if lam is not None:
+        buffer.process_gae(gamma, lam, policy.values(obs_n.contiguous()))
     trunc, col, tar = env._counter_totals()                # one read of the three counters
     stats = {"trunc": trunc, "col": col, "tar": tar}
     env._num_trunc = env._num_col = env._num_tar = 0      # models.py:153-158
     return mean, stats
 
 
-def collect_fused(env, policy, buffer, eps=None, gamma=0.9):
+def collect_fused(env, policy, buffer, eps=None, gamma=0.9, gae_lambda=None):
     """``collect`` as ONE C call (libmarlnav.so ``marlnav_rollout_collect``):
     the initial observations and their normalisation, then for each of the
     ``buffer.buffer_len`` steps the policy launch and the step launch, the
@@ -361,6 +452,12 @@ def collect_fused(env, policy, buffer, eps=None, gamma=0.9):
     then advances by the number of steps), or a ``(T, P*A, 2)`` float32
     tensor of standard normals, row ``t`` for step ``t``.
 
+    ``gae_lambda`` (None: the reference's estimator alone): three calls follow
+    the rollout call on the same stream with no synchronisation, as in
+    ``collect``: the normalised observations the env holds after the last
+    step (what the next rollout's row 0 will be), ``policy.values`` of them
+    and ``buffer.process_gae``.
+
     Tensors the caller still holds from before the call (``env.states``,
     ``obstacles``, ``target``, ``_step_num``, ``_terminates``) are not
     written: the env moves to copies first, and the held ones keep their
@@ -373,7 +470,7 @@ def collect_fused(env, policy, buffer, eps=None, gamma=0.9):
     stream capture unless ``env.allow_graph_capture`` is set (then the
     episode counters are left alone and the stats are None: reading them
     would synchronise)."""
-    mean, capturing = _collect_fused_enqueue(env, policy, buffer, eps, gamma)
+    mean, capturing = _collect_fused_enqueue(env, policy, buffer, eps, gamma, gae_lambda)
     if capturing:
         return mean, None
     trunc, col, tar = env._counter_totals()                # one read of the three counters
@@ -381,11 +478,12 @@ def collect_fused(env, policy, buffer, eps=None, gamma=0.9):
     return mean, {"trunc": trunc, "col": col, "tar": tar}
 
 
-def _collect_fused_enqueue(env, policy, buffer, eps=None, gamma=0.9):
+def _collect_fused_enqueue(env, policy, buffer, eps=None, gamma=0.9, gae_lambda=None):
     """``collect_fused`` up to the episode counters, which are left alone:
     every check, the one C call and the host-side bookkeeping, with nothing
     that synchronises. -> (mean_rew, capturing)."""
     who = "collect_fused"
+    lam = None if gae_lambda is None else _check_lambda(gae_lambda)
     if env._rng != 'native' or env._init_sampler is not env._default_init_sampler:
         raise RuntimeError(f"{who} needs an env in native-RNG mode with its default init "
                            "sampler: a reference-RNG or user-assigned sampler is called on the "
@@ -439,11 +537,14 @@ def _collect_fused_enqueue(env, policy, buffer, eps=None, gamma=0.9):
     env._engine.rollout(abi.fn_addr(lib.marlnav_rollout_collect), bytes(pd), bytes(pb), bytes(r),
                         raw.data_ptr(), last.data_ptr(), T, policy.seed, policy.step_idx,
                         float(gamma))
-    del truncated, work, raw, last     # stream-ordered: reused after the kernels
+    del truncated, work, raw           # stream-ordered: reused after the kernels
     if eps is None:
         policy.step_idx += T
     buffer.commit(T)
     buffer.returns = returns
+    if lam is not None:                # `last`: the observations after step T - 1, normalised
+        buffer.process_gae(gamma, lam, policy.values(last))
+    del last
     env._reinit_mask = torch.where(buffer.stacked(buffer.DONE)[T - 1], 1, 0)   # environment.py:102
     return stats[0], capturing
 
@@ -487,9 +588,20 @@ class FusedPPO(object):
     reference's ``repeat(num_agents)``, kept), which pairs rows across env
     shards; training over ``shard``-split envs needs an all-reduce of the
     gradients and a cross-shard reading of that pairing, neither of which is
-    here."""
+    here.
 
-    def __init__(self, actor, critic, epsilon, ent_const):
+    ``advantage='gae'`` (the default ``'reference'`` is the
+    above, bit for bit): the actor reads ``buffer.advantages`` as the ready
+    advantage of each agent row's OWN env row (``i // A``), the critic is
+    trained towards ``buffer.value_targets``; both come from
+    ``buffer.process_gae`` (``collect(..., gae_lambda=...)``). The own-env
+    pairing removes the cross-shard reading; the all-reduce is still missing."""
+
+    def __init__(self, actor, critic, epsilon, ent_const, advantage='reference'):
+        if advantage not in ('reference', 'gae'):
+            raise ValueError(f"advantage must be 'reference' or 'gae', got {advantage!r}")
+        self.advantage = advantage
+        self._mode = abi.ADVANTAGE_ENV if advantage == 'gae' else abi.ADVANTAGE_REFERENCE
         self.actor, self.critic = actor, critic
         self._params, self.device, H, D, A = _module_params(actor, critic, "FusedPPO")
         self.hidden_size, self.obs_dim, self.num_agents = H, D, A
@@ -502,11 +614,27 @@ class FusedPPO(object):
             if t.grad is None:
                 t.grad = torch.zeros_like(t)
 
-    def _bind(self, buffer, lo, hi):
-        """Point the call's structs at steps lo..hi of the buffer; -> loss."""
-        if buffer.returns is None:
+    def _require(self, buffer):
+        """Refuse a buffer that lacks what this mode trains on."""
+        if self.advantage == 'gae':
+            if buffer.advantages is None or buffer.value_targets is None:
+                raise RuntimeError("the rollout buffer has no GAE advantages yet: call "
+                                   "buffer.process_gae(gamma, lam, last_values) (or collect(..., "
+                                   "gae_lambda=...)) before training")
+        elif buffer.returns is None:
             raise RuntimeError("the rollout buffer has no returns yet: call "
                                "buffer.process_rewards(gamma) (or collect()) before training")
+
+    def _bind(self, buffer, lo, hi, network='actor'):
+        """Point the call's structs at steps lo..hi of the buffer; -> loss.
+        The ``returns`` pointer: the normalised returns, or in the GAE mode
+        the advantages (``network='actor'``) / the value targets
+        (``'critic'``)."""
+        self._require(buffer)
+        if self.advantage == 'gae':
+            target = buffer.advantages if network == 'actor' else buffer.value_targets
+        else:
+            target = buffer.returns
         n = len(buffer)
         lo, hi = int(lo), int(hi)
         if not 0 <= lo < hi <= n:
@@ -519,7 +647,7 @@ class FusedPPO(object):
                                       ("actions", actions, (n, P, A, 2), torch.float32),
                                       ("log_probs", log_probs, (n, P * A), torch.float32),
                                       ("values", values, (n, P, 1), torch.float32),
-                                      ("returns", buffer.returns, (n, P), _F64)):
+                                      ("returns", target, (n, P), _F64)):
             if (tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device
                     or not t.is_contiguous()):
                 raise ValueError(f"buffer {name}: need a contiguous {dtype} {shape} tensor on "
@@ -550,15 +678,15 @@ class FusedPPO(object):
         ``buffer``; the six actor parameters' ``.grad`` are overwritten. Two
         launches on the current stream, no synchronisation."""
         loss = self._bind(buffer, lo, hi)
-        abi.check(self._lib.marlnav_ppo_actor_grad(
+        abi.check(self._lib.marlnav_ppo_actor_grad_mode(
             ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon, self.ent_const,
-            _stream(self.device)), self._lib)
+            self._mode, _stream(self.device)), self._lib)
         return loss
 
     def critic_loss_grad(self, buffer, lo, hi):
         """Critic loss (0-d float64 device tensor) of steps ``lo..hi``; the
         four critic parameters' ``.grad`` are overwritten."""
-        loss = self._bind(buffer, lo, hi)
+        loss = self._bind(buffer, lo, hi, 'critic')
         abi.check(self._lib.marlnav_ppo_critic_grad(
             ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon,
             _stream(self.device)), self._lib)
@@ -578,16 +706,16 @@ class FusedPPO(object):
         table). Returns the loss (0-d float64 device tensor)."""
         loss = self._bind(buffer, lo, hi)
         ad, ab = adam._bind()
-        abi.check(self._lib.marlnav_ppo_actor_update(
+        abi.check(self._lib.marlnav_ppo_actor_update_mode(
             ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon, self.ent_const,
-            ctypes.byref(ad), ctypes.byref(ab), _stream(self.device)), self._lib)
+            ctypes.byref(ad), ctypes.byref(ab), self._mode, _stream(self.device)), self._lib)
         return loss
 
     def critic_update(self, buffer, lo, hi, adam):
         """``critic_loss_grad`` then ``adam.step()`` as one C call
         (``marlnav_ppo_critic_update``); ``adam`` over the four critic
         parameters. As ``actor_update``."""
-        loss = self._bind(buffer, lo, hi)
+        loss = self._bind(buffer, lo, hi, 'critic')
         ad, ab = adam._bind()
         abi.check(self._lib.marlnav_ppo_critic_update(
             ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon,
@@ -783,10 +911,8 @@ class FusedAdam(object):
         self._hyper()
 
 
-def _train(loss_grad, update, network, buffer, optimizer, num_epochs, batch_size, log):
-    if buffer.returns is None:
-        raise RuntimeError("the rollout buffer has no returns yet: call "
-                           "buffer.process_rewards(gamma) (or collect()) before training")
+def _train(ppo, loss_grad, update, network, buffer, optimizer, num_epochs, batch_size, log):
+    ppo._require(buffer)
     bounds = minibatch_bounds(len(buffer), batch_size)
     # a FusedAdam over exactly this network's parameters: one C call per
     # minibatch; any other optimiser: the two calls
@@ -814,11 +940,11 @@ def train_actor(ppo, buffer, optimizer, num_epochs, batch_size, log=None):
     reference's module) the two calls of a minibatch become the one call
     ``ppo.actor_update``, with equal bits, and a whole epoch can be captured
     in a graph."""
-    _train(ppo.actor_loss_grad, ppo.actor_update, ppo._network_params("actor"), buffer,
+    _train(ppo, ppo.actor_loss_grad, ppo.actor_update, ppo._network_params("actor"), buffer,
            optimizer, num_epochs, batch_size, log)
 
 
 def train_critic(ppo, buffer, optimizer, num_epochs, batch_size, log=None):
     """MAPPO.train_critic (models.py:180-198), as ``train_actor``."""
-    _train(ppo.critic_loss_grad, ppo.critic_update, ppo._network_params("critic"), buffer,
+    _train(ppo, ppo.critic_loss_grad, ppo.critic_update, ppo._network_params("critic"), buffer,
            optimizer, num_epochs, batch_size, log)

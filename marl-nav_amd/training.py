@@ -164,9 +164,7 @@ def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None):
             abi.NETWORK_ACTOR: abi.NETWORK_ACTOR, abi.NETWORK_CRITIC: abi.NETWORK_CRITIC}
     if network not in nets:
         raise ValueError(f"network must be 'actor' or 'critic', got {network!r}")
-    if buffer.returns is None:
-        raise RuntimeError("the rollout buffer has no returns yet: call "
-                           "buffer.process_rewards(gamma) (or collect()) before training")
+    ppo._require(buffer)
     lib, dev = ppo._lib, ppo.device
     bounds = minibatch_bounds(len(buffer), batch_size)
     B, E = len(bounds), int(num_epochs)
@@ -181,7 +179,8 @@ def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None):
             or not out.is_contiguous()):
         raise ValueError(f"out: need a contiguous float64 tensor of {E * B} elements on {dev}")
     arr = (ctypes.c_int64 * (2 * B))(*[x for b in bounds for x in b])
-    ppo._bind(buffer, 0, len(buffer))       # step 0 of the storage, dims of the whole buffer
+    # step 0 of the storage, dims of the whole buffer
+    ppo._bind(buffer, 0, len(buffer), 'actor' if nets[network] == abi.NETWORK_ACTOR else 'critic')
     d, b = ppo._dims, ppo._bufs
     need = int(lib.marlnav_ppo_train_work_size(ctypes.byref(d), arr, B))
     if need < 0:
@@ -190,9 +189,9 @@ def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None):
         ppo._work = torch.empty(need, dtype=_F64, device=dev)
     b.work = ppo._work.data_ptr()
     ad, ab = adam._bind()
-    abi.check(lib.marlnav_ppo_train_phase(
+    abi.check(lib.marlnav_ppo_train_phase_mode(
         nets[network], ctypes.byref(d), ctypes.byref(b), arr, B, E, ppo.epsilon, ppo.ent_const,
-        ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(),
+        ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(), ppo._mode,
         torch._C._cuda_getCurrentRawStream(dev.index)), lib)
     return out
 
@@ -206,6 +205,14 @@ class MAPPO(object):
     normaliser / action scaler where ``params`` has none to attach
     (``params['normalizer']`` / ``params['scaler']`` are attached to an env
     that has none, as ``--evaluate`` does).
+
+    ``params['gae_lambda']`` (absent or None: the reference's estimator, bit
+    for bit) selects the GAE(lambda) advantage mode of DESIGN.md §15: every
+    rollout is followed by the bootstrap value and the GAE scan, the actor
+    trains on own-env advantages and the critic towards the value targets.
+    The mean-reward log and the checkpoint rule still read the reference's
+    returns, so they mean the same in both modes. A value outside [0, 1] is a
+    ValueError.
 
     ``seed`` keys the policy kernel's normals (``FusedPolicy``); the modules'
     initial weights come from torch's global generator, as the reference's do.
@@ -226,6 +233,10 @@ class MAPPO(object):
 
     def __init__(self, params, env, seed=0, track_best=False, out_dir='.'):
         who = "MAPPO"
+        # the advantage mode, before anything touches the env
+        self.gae_lambda = params.get('gae_lambda')
+        if self.gae_lambda is not None:
+            self.gae_lambda = rollout._check_lambda(self.gae_lambda)
         if env._rng != 'native' or env._init_sampler is not env._default_init_sampler:
             raise RuntimeError(f"{who} needs an env in native-RNG mode with its default init "
                                "sampler: a reference-RNG or user-assigned sampler is called on "
@@ -268,7 +279,8 @@ class MAPPO(object):
                              f"buffer_len={self.buffer_len}: no minibatch")
         self.buffer = RolloutBuffer(self.buffer_len)
         self.policy = FusedPolicy(self.actor, self.critic, seed=seed)
-        self.ppo = FusedPPO(self.actor, self.critic, self.epsilon, self.ent_const)
+        self.ppo = FusedPPO(self.actor, self.critic, self.epsilon, self.ent_const,
+                            advantage='reference' if self.gae_lambda is None else 'gae')
         self.track_best = bool(track_best)
         self.out_dir = out_dir
         self._time = datetime.now().strftime('%Y%m%d%H%M%S')
@@ -359,7 +371,8 @@ class MAPPO(object):
         r = self._r
         self._reserve(r + 1)
         env, lib = self.env, self._lib
-        mean, _ = rollout._collect_fused_enqueue(env, self.policy, self.buffer, gamma=self.gamma)
+        mean, _ = rollout._collect_fused_enqueue(env, self.policy, self.buffer, gamma=self.gamma,
+                                                 gae_lambda=self.gae_lambda)
         self._mean_rew = mean
         self._mean_log[r].copy_(mean)
         abi.check(lib.marlnav_counters_total(ctypes.byref(env._dims), env._counters.data_ptr(),

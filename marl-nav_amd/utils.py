@@ -172,6 +172,8 @@ def set_model_params(args, device):
     if args.num_total % (args.buffer_len * args.num_parallel) != 0:
         raise ValueError('num_total should be divisible with (buffer_len * num_parallel).')
     obs_size = 2 + 2 * args.num_obstacles + 2 * (args.num_agents - 1)
+    # marlnav_amd only: the GAE(lambda) advantage mode, present only when asked for
+    gae = {} if getattr(args, 'gae_lambda', None) is None else {'gae_lambda': args.gae_lambda}
     return {
         'actor': {'input_size': obs_size, 'hidden_size': args.hidden_size},
         'critic': {'input_size': obs_size * args.num_agents, 'hidden_size': args.hidden_size},
@@ -189,6 +191,7 @@ def set_model_params(args, device):
         'action_size': 2,
         'normalizer': set_normalizer_params(args, device),
         'scaler': set_scaler_params(args, device),
+        **gae,
     }
 
 
