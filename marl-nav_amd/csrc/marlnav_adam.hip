@@ -35,6 +35,7 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -44,6 +45,8 @@
 __attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const char *msg);
 
 namespace {
+
+#include "host_util.h"
 
 constexpr int kThreads = 256;
 constexpr int kSlots = MARLNAV_ADAM_MAX_TENSORS;
@@ -132,60 +135,41 @@ __global__ void __launch_bounds__(kThreads) adam_apply(AdamArgs a)
 }
 
 // ---- host side
-int fail_slot(const char *fmt, int slot, long long value)
-{
-    char msg[256];
-    snprintf(msg, sizeof(msg), fmt, slot, value);
-    return marlnav_internal_fail(MARLNAV_EINVAL, msg);
-}
-
-int fail_real(const char *fmt, double value)
-{
-    char msg[256];
-    snprintf(msg, sizeof(msg), fmt, value);
-    return marlnav_internal_fail(MARLNAV_EINVAL, msg);
-}
-
 inline uintptr_t addr(const void *p) { return reinterpret_cast<uintptr_t>(p); }
 
 int check_adam(const MarlnavAdamDims *d, const MarlnavAdamBuffers *b)
 {
     if (!d) return marlnav_internal_fail(MARLNAV_EINVAL, "adam dims is NULL");
     if (d->num_tensors < 1 || d->num_tensors > kSlots)
-        return fail_slot("adam: num_tensors=%d outside [1, %lld]", d->num_tensors, kSlots);
+        return failf(MARLNAV_EINVAL, "adam: num_tensors=%d outside [1, %d]", d->num_tensors, kSlots);
     if (d->maximize != 0 && d->maximize != 1)
-        return fail_slot("adam: maximize=%d must be 0 or 1", d->maximize, 0);
+        return failf(MARLNAV_EINVAL, "adam: maximize=%d must be 0 or 1", d->maximize);
     int64_t total = 0;
     for (int i = 0; i < d->num_tensors; ++i) {
-        if (d->numel[i] < 1) return fail_slot("adam: numel[%d]=%lld < 1", i, d->numel[i]);
+        if (d->numel[i] < 1) return failf(MARLNAV_EINVAL, "adam: numel[%d]=%lld < 1", i, (long long)d->numel[i]);
         if (d->numel[i] > kMaxElements - total)
-            return fail_slot("adam: numel[%d]=%lld brings the table past 2^40 elements", i,
-                             d->numel[i]);
+            return failf(MARLNAV_EINVAL, "adam: numel[%d]=%lld brings the table past 2^40 elements",
+                         i, (long long)d->numel[i]);
         total += d->numel[i];
     }
     if (!(d->lr >= 0.0) || !__builtin_isfinite(d->lr))
-        return fail_real("adam: lr=%g must be finite and >= 0", d->lr);
+        return failf(MARLNAV_EINVAL, "adam: lr=%g must be finite and >= 0", d->lr);
     if (!(d->beta1 >= 0.0 && d->beta1 < 1.0))
-        return fail_real("adam: beta1=%g outside [0, 1)", d->beta1);
+        return failf(MARLNAV_EINVAL, "adam: beta1=%g outside [0, 1)", d->beta1);
     if (!(d->beta2 >= 0.0 && d->beta2 < 1.0))
-        return fail_real("adam: beta2=%g outside [0, 1)", d->beta2);
+        return failf(MARLNAV_EINVAL, "adam: beta2=%g outside [0, 1)", d->beta2);
     if (!(d->eps >= 0.0) || !__builtin_isfinite(d->eps))
-        return fail_real("adam: eps=%g must be finite and >= 0", d->eps);
+        return failf(MARLNAV_EINVAL, "adam: eps=%g must be finite and >= 0", d->eps);
     if (d->reserved != 0)
-        return fail_real("adam: reserved=%.0f must be 0", (double)d->reserved);
+        return failf(MARLNAV_EINVAL, "adam: reserved=%lld must be 0", (long long)d->reserved);
     if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "adam buffers is NULL");
     for (int i = 0; i < d->num_tensors; ++i) {
         const void *ptr[4] = {b->param[i], b->grad[i], b->exp_avg[i], b->exp_avg_sq[i]};
-        const char *null_fmt[4] = {"adam: buffer param[%d] is NULL", "adam: buffer grad[%d] is NULL",
-                                   "adam: buffer exp_avg[%d] is NULL",
-                                   "adam: buffer exp_avg_sq[%d] is NULL"};
-        const char *align_fmt[4] = {"adam: buffer param[%d] must be 4-byte aligned",
-                                    "adam: buffer grad[%d] must be 4-byte aligned",
-                                    "adam: buffer exp_avg[%d] must be 4-byte aligned",
-                                    "adam: buffer exp_avg_sq[%d] must be 4-byte aligned"};
+        const char *name[4] = {"param", "grad", "exp_avg", "exp_avg_sq"};
         for (int k = 0; k < 4; ++k) {
-            if (!ptr[k]) return fail_slot(null_fmt[k], i, 0);
-            if (addr(ptr[k]) & 3u) return fail_slot(align_fmt[k], i, 0);
+            if (!ptr[k]) return failf(MARLNAV_EINVAL, "adam: buffer %s[%d] is NULL", name[k], i);
+            if (addr(ptr[k]) & 3u)
+                return failf(MARLNAV_EINVAL, "adam: buffer %s[%d] must be 4-byte aligned", name[k], i);
         }
     }
     if (!b->state) return marlnav_internal_fail(MARLNAV_EINVAL, "adam: buffer state is NULL");
@@ -227,9 +211,7 @@ int enqueue_adam(const MarlnavAdamDims *d, const MarlnavAdamBuffers *b, hipStrea
     // items <= 2^38 + 8: the grid fits 31 bits
     hipLaunchKernelGGL(adam_apply, dim3((unsigned)((items + kThreads - 1) / kThreads)),
                        dim3(kThreads), 0, s, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 // The Adam table of an update call must be the network's own: slot i is the
@@ -238,27 +220,19 @@ int check_table(const char *net, int count, const float *const *w, float *const 
                 const int64_t *size, const char *const *name, const MarlnavAdamDims *ad,
                 const MarlnavAdamBuffers *ab)
 {
-    char msg[256];
-    if (ad->num_tensors != count) {
-        snprintf(msg, sizeof(msg), "adam table: num_tensors=%d, the %s has %d parameters",
-                 ad->num_tensors, net, count);
-        return marlnav_internal_fail(MARLNAV_EINVAL, msg);
-    }
+    if (ad->num_tensors != count)
+        return failf(MARLNAV_EINVAL, "adam table: num_tensors=%d, the %s has %d parameters",
+                     ad->num_tensors, net, count);
     for (int i = 0; i < count; ++i) {
-        if (ab->param[i] != w[i]) {
-            snprintf(msg, sizeof(msg), "adam table: param[%d] is not the ppo buffer %s", i, name[i]);
-            return marlnav_internal_fail(MARLNAV_EINVAL, msg);
-        }
-        if (ab->grad[i] != gw[i]) {
-            snprintf(msg, sizeof(msg), "adam table: grad[%d] is not the ppo buffer grad_%s", i,
-                     name[i]);
-            return marlnav_internal_fail(MARLNAV_EINVAL, msg);
-        }
-        if (ad->numel[i] != size[i]) {
-            snprintf(msg, sizeof(msg), "adam table: numel[%d]=%lld, %s has %lld elements", i,
-                     (long long)ad->numel[i], name[i], (long long)size[i]);
-            return marlnav_internal_fail(MARLNAV_EINVAL, msg);
-        }
+        if (ab->param[i] != w[i])
+            return failf(MARLNAV_EINVAL, "adam table: param[%d] is not the ppo buffer %s", i,
+                         name[i]);
+        if (ab->grad[i] != gw[i])
+            return failf(MARLNAV_EINVAL, "adam table: grad[%d] is not the ppo buffer grad_%s", i,
+                         name[i]);
+        if (ad->numel[i] != size[i])
+            return failf(MARLNAV_EINVAL, "adam table: numel[%d]=%lld, %s has %lld elements", i,
+                         (long long)ad->numel[i], name[i], (long long)size[i]);
     }
     return 0;
 }
@@ -343,28 +317,19 @@ __attribute__((visibility("hidden"))) int marlnav_internal_ppo_fold(
 
 namespace {
 
-int fail_ll(const char *fmt, long long a, long long b, long long c)
-{
-    char msg[256];
-    snprintf(msg, sizeof(msg), fmt, a, b, c);
-    return marlnav_internal_fail(MARLNAV_EINVAL, msg);
-}
-
 // the (lo, hi) list against the buffer's steps
 int check_bounds(const MarlnavPpoDims *d, const int64_t *bounds, int64_t num_batches)
 {
     if (num_batches < 1)
-        return fail_ll("train: num_batches=%lld < 1", num_batches, 0, 0);
+        return failf(MARLNAV_EINVAL, "train: num_batches=%lld < 1", (long long)num_batches);
     if (!bounds) return marlnav_internal_fail(MARLNAV_EINVAL, "train: bounds is NULL");
     for (int64_t j = 0; j < num_batches; ++j) {
         const int64_t lo = bounds[2 * j], hi = bounds[2 * j + 1];
-        if (lo < 0 || hi <= lo || hi > d->num_steps) {
-            char msg[256];
-            snprintf(msg, sizeof(msg),
-                     "train: bounds[%lld]=(%lld, %lld) is not a non-empty range of the %lld steps",
-                     (long long)j, (long long)lo, (long long)hi, (long long)d->num_steps);
-            return marlnav_internal_fail(MARLNAV_EINVAL, msg);
-        }
+        if (lo < 0 || hi <= lo || hi > d->num_steps)
+            return failf(MARLNAV_EINVAL,
+                         "train: bounds[%lld]=(%lld, %lld) is not a non-empty range of the %lld "
+                         "steps", (long long)j, (long long)lo, (long long)hi,
+                         (long long)d->num_steps);
     }
     return 0;
 }
@@ -414,17 +379,16 @@ extern "C" int marlnav_ppo_train_phase_mode(int network, const MarlnavPpoDims *d
 {
     // ---- every check before the first launch
     if (network != MARLNAV_NETWORK_ACTOR && network != MARLNAV_NETWORK_CRITIC)
-        return fail_ll("train: network=%lld must be MARLNAV_NETWORK_ACTOR or _CRITIC", network, 0,
-                       0);
+        return failf(MARLNAV_EINVAL, "train: network=%d must be MARLNAV_NETWORK_ACTOR or _CRITIC", network);
     if (advantage_mode != MARLNAV_ADVANTAGE_REFERENCE && advantage_mode != MARLNAV_ADVANTAGE_ENV)
-        return fail_ll("train: advantage_mode=%lld must be MARLNAV_ADVANTAGE_REFERENCE or _ENV",
-                       advantage_mode, 0, 0);
+        return failf(MARLNAV_EINVAL, "train: advantage_mode=%d must be MARLNAV_ADVANTAGE_REFERENCE or _ENV",
+                     advantage_mode);
     // the own-env pairing is the actor's: it reads no values
     const bool need_values =
         network == MARLNAV_NETWORK_CRITIC || advantage_mode == MARLNAV_ADVANTAGE_REFERENCE;
     if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
     if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
-    if (num_epochs < 1) return fail_ll("train: num_epochs=%lld < 1", num_epochs, 0, 0);
+    if (num_epochs < 1) return failf(MARLNAV_EINVAL, "train: num_epochs=%lld < 1", (long long)num_epochs);
     int rc = check_bounds(d, bounds, num_batches);
     if (rc) return rc;
     if (!loss_log) return marlnav_internal_fail(MARLNAV_EINVAL, "train: loss_log is NULL");
@@ -562,21 +526,21 @@ extern "C" int marlnav_params_snapshot_if(int num_tensors, const float *const *s
                                           int track_best, void *stream)
 {
     if (num_tensors < 1 || num_tensors > kSnapSlots)
-        return fail_slot("snapshot: num_tensors=%d outside [1, %lld]", num_tensors, kSnapSlots);
+        return failf(MARLNAV_EINVAL, "snapshot: num_tensors=%d outside [1, %d]", num_tensors, kSnapSlots);
     if (!src) return marlnav_internal_fail(MARLNAV_EINVAL, "snapshot: src is NULL");
     if (!dst) return marlnav_internal_fail(MARLNAV_EINVAL, "snapshot: dst is NULL");
     if (!numel) return marlnav_internal_fail(MARLNAV_EINVAL, "snapshot: numel is NULL");
     int64_t total = 0;
     for (int i = 0; i < num_tensors; ++i) {
-        if (numel[i] < 1) return fail_slot("snapshot: numel[%d]=%lld < 1", i, numel[i]);
+        if (numel[i] < 1) return failf(MARLNAV_EINVAL, "snapshot: numel[%d]=%lld < 1", i, (long long)numel[i]);
         if (numel[i] > kMaxElements - total)
-            return fail_slot("snapshot: numel[%d]=%lld brings the table past 2^40 elements", i,
-                             numel[i]);
+            return failf(MARLNAV_EINVAL, "snapshot: numel[%d]=%lld brings the table past 2^40 elements",
+                         i, (long long)numel[i]);
         total += numel[i];
-        if (!src[i]) return fail_slot("snapshot: src[%d] is NULL", i, 0);
-        if (!dst[i]) return fail_slot("snapshot: dst[%d] is NULL", i, 0);
-        if (addr(src[i]) & 3u) return fail_slot("snapshot: src[%d] must be 4-byte aligned", i, 0);
-        if (addr(dst[i]) & 3u) return fail_slot("snapshot: dst[%d] must be 4-byte aligned", i, 0);
+        if (!src[i]) return failf(MARLNAV_EINVAL, "snapshot: src[%d] is NULL", i);
+        if (!dst[i]) return failf(MARLNAV_EINVAL, "snapshot: dst[%d] is NULL", i);
+        if (addr(src[i]) & 3u) return failf(MARLNAV_EINVAL, "snapshot: src[%d] must be 4-byte aligned", i);
+        if (addr(dst[i]) & 3u) return failf(MARLNAV_EINVAL, "snapshot: dst[%d] must be 4-byte aligned", i);
     }
     if (!mean_rew) return marlnav_internal_fail(MARLNAV_EINVAL, "snapshot: mean_rew is NULL");
     if (!max_rew) return marlnav_internal_fail(MARLNAV_EINVAL, "snapshot: max_rew is NULL");
@@ -585,9 +549,9 @@ extern "C" int marlnav_params_snapshot_if(int num_tensors, const float *const *s
         return marlnav_internal_fail(
             MARLNAV_EINVAL, "snapshot: mean_rew, max_rew and save_state must be 8-byte aligned");
     if (repeat_index < 0)
-        return fail_ll("snapshot: repeat_index=%lld < 0", repeat_index, 0, 0);
+        return failf(MARLNAV_EINVAL, "snapshot: repeat_index=%lld < 0", (long long)repeat_index);
     if (track_best != 0 && track_best != 1)
-        return fail_slot("snapshot: track_best=%d must be 0 or 1", track_best, 0);
+        return failf(MARLNAV_EINVAL, "snapshot: track_best=%d must be 0 or 1", track_best);
 
     SnapArgs a;
     int64_t items = 0;
@@ -610,7 +574,5 @@ extern "C" int marlnav_params_snapshot_if(int num_tensors, const float *const *s
                        dim3(kThreads), 0, s, a);
     hipLaunchKernelGGL(snapshot_book, dim3(1), dim3(64), 0, s, mean_rew, max_rew, save_state,
                        repeat_index, track_best);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }

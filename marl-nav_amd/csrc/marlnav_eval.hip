@@ -5,12 +5,15 @@
 //
 // marlnav_actor_act: Actor.forward (models.py:27-36) and dist.loc or
 // dist.sample() for all P*A agent rows in one launch. It is the actor third
-// of policy_kernel (marlnav_policy.hip) restated: the same collapse
+// of policy_kernel (marlnav_policy.hip): the collapse
 //   Weff = [Wmu; Wstd] W1 (4 x D), beff = [Wmu; Wstd] b1 + [bmu; bstd]
 // recomputed per block from the live weight tensors (four waves each summing
 // their quarter of the hidden units in groups of eight, the partials added in
-// wave order), and the same four FMA chains per row (from beff, k ascending),
-// so an action here has the bits marlnav_policy_act gives it. What is gone is
+// wave order) on policy_forward.h's LDS layout, then that header's row_chains
+// (from beff, k ascending) and sample_action, so an action here has the bits
+// marlnav_policy_act gives it. The collapse is policy_forward.h's written out
+// in the kernel (measured: the comment there).
+// What is gone is
 // the critic (at 16 agents x 32 obstacles a 307 KB first layer streamed per
 // 64 envs) and, in MEAN mode, everything after tanh. A block owns
 // kRowsPerBlock consecutive agent rows whatever env they belong to; every
@@ -24,7 +27,7 @@
 // marlnav_rollout_evaluate chains them with the existing observe / step
 // launches, as marlnav_rollout_collect (marlnav_rollout.hip) chains a rollout.
 //
-// Built with -ffp-contract=off: every FMA below is explicit.
+// Built with -ffp-contract=off: every FMA is explicit.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -38,20 +41,12 @@ __attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const 
 
 namespace {
 
-#include "device_rng.h"
+#include "policy_forward.h"
+#include "host_util.h"
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
 constexpr int kRowsPerBlock = kThreads;  // agent rows of a block: one per thread (measured
                                          // against 64, 128, 512, 1024: DESIGN.md §13)
-constexpr int kMaxAgentsP = 64, kMaxObstP = 256, kMaxHidden = 512;
-constexpr int kMaxD = 2 * kMaxAgentsP + 2 * kMaxObstP;  // 640
-// dynamic LDS floats of a block: Weff and its kWaves partials (4 D each),
-// beff and its partials
-constexpr size_t lds_floats(int D) { return (size_t)(1 + kWaves) * 4 * D + 4 + 4 * kWaves; }
-static_assert(kRowsPerBlock == kThreads, "one row per thread");
-static_assert(lds_floats(kMaxD) * sizeof(float) <= 64 * 1024, "LDS of the widest row");
-constexpr uint32_t kPolicyBlock = 0x80000000u;  // Philox block-index domain of the policy's normals
+static_assert(collapse_lds_floats(kMaxD) * sizeof(float) <= 64 * 1024, "LDS of the widest row");
 
 struct ActorArgs {
     const float *obs_norm, *fc1_w, *fc1_b, *mu_w, *mu_b, *std_w, *std_b, *eps;
@@ -63,80 +58,39 @@ struct ActorArgs {
     uint64_t step;
 };
 
-// N consecutive floats at p into registers with the widest loads N allows
-// (the caller guarantees p is 16-byte aligned when N % 4 == 0, 8-byte when
-// N % 2 == 0: obs is 16-byte aligned and rows are N floats apart)
-template <int N>
-__device__ __forceinline__ void load_row(const float *__restrict__ p, float (&x)[N])
-{
-    if constexpr (N % 4 == 0) {
-#pragma unroll
-        for (int i = 0; i < N / 4; ++i) {
-            const float4 v = reinterpret_cast<const float4 *>(p)[i];
-            x[4 * i] = v.x, x[4 * i + 1] = v.y, x[4 * i + 2] = v.z, x[4 * i + 3] = v.w;
-        }
-    } else if constexpr (N % 2 == 0) {
-#pragma unroll
-        for (int i = 0; i < N / 2; ++i) {
-            const float2 v = reinterpret_cast<const float2 *>(p)[i];
-            x[2 * i] = v.x, x[2 * i + 1] = v.y;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; ++i) x[i] = p[i];
-    }
-}
-
-// torch.nn.functional.softplus (beta 1, threshold 20)
-__device__ __forceinline__ float softplus_t(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
-
-// two standard normals of global agent row gid at step s, as policy_kernel
-// draws them: Box-Muller on the two words of one Philox block, u1 in (0, 1],
-// u2 in [0, 1) on the 24-bit grid
-__device__ __forceinline__ void policy_normals(uint64_t seed, uint64_t gid, uint64_t s, float &z0,
-                                               float &z1)
-{
-    uint32_t r0, r1;
-    native_block(seed, kPolicyBlock, gid, s, r0, r1);
-    const float u1 = (float)((r0 >> 8) + 1u) * 0x1.0p-24f;
-    const float u2 = native_u24(r1);
-    const float rad = sqrtf(-2.0f * logf(u1));
-    // v_sin_f32 / v_cos_f32 take the angle in revolutions: no range reduction
-    z0 = rad * __builtin_amdgcn_cosf(u2);
-    z1 = rad * __builtin_amdgcn_sinf(u2);
-}
-
 // D_T: compiled row length (0: run-time D, inputs read from memory as used)
 template <int D_T, int MODE>
 __global__ void __launch_bounds__(kThreads) actor_kernel(ActorArgs g)
 {
     const int D = D_T ? D_T : g.D;
-    const int H = g.H;
     const float *__restrict__ obs = g.obs_norm;
 
-    // LDS, all in the dynamic region (16-byte aligned base and offsets):
-    // Weff as [k][4], the four waves' partial Weff, beff, its partials
+    // LDS, all in the dynamic region (the layout of policy_forward.h): Weff as
+    // [k][4], the four waves' partial Weff, beff, its partials
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
     float *s_w = s_dyn;
-    float *s_wp = s_w + 4 * D;
-    float *s_b = s_wp + kWaves * 4 * D;
-    float *s_bp = s_b + 4;
+    float *s_wp = lds_wp(s_dyn, D);
+    float *s_b = lds_b(s_dyn, D);
+    float *s_bp = lds_bp(s_dyn, D);
 
     const int t = threadIdx.x;
     const int q = __builtin_amdgcn_readfirstlane(t >> 6);  // wave of the block
     const int lane = t & 63;
-    // wave q's share of the hidden units
-    const int Hq = (H + kWaves - 1) / kWaves;
-    const int j0 = q * Hq, j1 = (j0 + Hq < H) ? j0 + Hq : H;
+    const int H = g.H;
+    int j0, j1;
+    wave_share(H, q, j0, j1);
 
-    // ---- collapse the actor, operation for operation as policy_kernel does:
-    // Weff[r][k] = sum_j head_r[j] W1[j][k], each wave summing its hidden
-    // units with the loads of a group of 8 issued before the first FMA
+    // ---- the collapse: collapse_partials and collapse_sum (policy_forward.h)
+    // written out, operation for operation. Called as functions they gave
+    // actor_kernel<0, *> the same instructions in another order on 54 VGPRs
+    // for 42, 0.06-0.08 us slower at 4 096 x 16 x 32 in every pass (9.99 / 10.78
+    // against 9.94 / 10.70 us, mean / sample); written out the six kernels
+    // compile to the code they had (DESIGN.md §13,
+    // profiles/policy_share_bench.txt). tests/test_evaluate_gpu.py holds the two
+    // to equal bits.
     {
         const float *__restrict__ w1 = g.fc1_w;
         const float *__restrict__ b1 = g.fc1_b;
-        // rows 0..4D-1: Weff[r][k] with r = idx / D, k = idx % D; then four
-        // rows for beff's sums over fc1.bias (the same code with b1 for W1)
         for (int idx = lane; idx < 4 * D + 4; idx += 64) {
             const bool bias = idx >= 4 * D;
             const int r = bias ? idx - 4 * D : idx / D;
@@ -180,58 +134,20 @@ __global__ void __launch_bounds__(kThreads) actor_kernel(ActorArgs g)
     }
     __syncthreads();  // Weff and beff are in LDS
 
-    // ---- one thread per agent row: the chains start from beff, k ascending
-    // (MEAN never reads the two covariance chains, so they are not formed)
+    // ---- one thread per agent row (MEAN never reads the two covariance
+    // chains, so they are not formed)
     const int64_t row = (int64_t)blockIdx.x * kRowsPerBlock + t;
     const float4 be = *reinterpret_cast<const float4 *>(s_b);
     if (row < g.rows) {
-        const float *__restrict__ xr = obs + row * D;
-        float p0 = be.x, p1 = be.y, p2 = be.z, p3 = be.w;
-        if constexpr (D_T != 0) {
-            float x[D_T];
-            load_row<D_T>(xr, x);
-#pragma unroll
-            for (int k = 0; k < D_T; ++k) {
-                const float4 w = *reinterpret_cast<const float4 *>(s_w + 4 * k);
-                p0 = __builtin_fmaf(w.x, x[k], p0);
-                p1 = __builtin_fmaf(w.y, x[k], p1);
-                if constexpr (MODE == MARLNAV_ACT_SAMPLE) {
-                    p2 = __builtin_fmaf(w.z, x[k], p2);
-                    p3 = __builtin_fmaf(w.w, x[k], p3);
-                }
-            }
-        } else {
-            for (int k = 0; k < D; ++k) {
-                const float4 w = *reinterpret_cast<const float4 *>(s_w + 4 * k);
-                const float xv = xr[k];
-                p0 = __builtin_fmaf(w.x, xv, p0);
-                p1 = __builtin_fmaf(w.y, xv, p1);
-                if constexpr (MODE == MARLNAV_ACT_SAMPLE) {
-                    p2 = __builtin_fmaf(w.z, xv, p2);
-                    p3 = __builtin_fmaf(w.w, xv, p3);
-                }
-            }
-        }
-        const float mu0 = tanhf(p0), mu1 = tanhf(p1);
+        const float4 p = row_chains<D_T, MODE == MARLNAV_ACT_SAMPLE>(obs + row * D, D, be, s_w);
+        const float mu0 = tanhf(p.x), mu1 = tanhf(p.y);
         if constexpr (MODE == MARLNAV_ACT_MEAN) {
             g.actions[2 * row] = mu0;  // dist.loc
             g.actions[2 * row + 1] = mu1;
         } else {
-            const float v0 = softplus_t(p2), v1 = softplus_t(p3);
             float e0, e1;
-            if (g.eps) {
-                e0 = g.eps[2 * row];
-                e1 = g.eps[2 * row + 1];
-            } else {
-                policy_normals(g.seed, (uint64_t)(g.row_base + row), g.step, e0, e1);
-            }
-            if (g.eps_out) {
-                g.eps_out[2 * row] = e0;
-                g.eps_out[2 * row + 1] = e1;
-            }
-            // loc + scale_tril @ eps: the product and the sum round separately
-            g.actions[2 * row] = mu0 + sqrtf(v0) * e0;
-            g.actions[2 * row + 1] = mu1 + sqrtf(v1) * e1;
+            sample_action(g.eps, g.eps_out, g.actions, mu0, mu1, softplus_t(p.z), softplus_t(p.w),
+                          row, g.seed, (uint64_t)(g.row_base + row), g.step, e0, e1);
         }
     }
 }
@@ -414,54 +330,12 @@ __global__ void __launch_bounds__(kThreads) eval_obs_norm_kernel(const float *__
     out[i] = (obs[i] - mean[k]) / scale[k];
 }
 
-int failf(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-int failf(int code, const char *fmt, ...)
-{
-    char msg[400];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, sizeof(msg), fmt, ap);
-    va_end(ap);
-    return marlnav_internal_fail(code, msg);
-}
-
-// a launch of step t failed inside `what`: its message, with the step named
-int fail_step(int code, int64_t t, const char *what)
-{
-    char inner[256];
-    snprintf(inner, sizeof(inner), "%s", marlnav_last_error());
-    return failf(code, "marlnav_rollout_evaluate: step %lld, %s: %s", (long long)t, what, inner);
-}
-
-int fail_launch(int64_t t, const char *what, hipError_t e)
-{
-    return failf(MARLNAV_ELAUNCH, "marlnav_rollout_evaluate: step %lld, %s: %s", (long long)t, what,
-                 hipGetErrorString(e));
-}
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
-// the shape checks of marlnav_policy_act, for `who`
+// the shape checks of marlnav_policy_act and the actor's grid limit, for `who`
 int check_policy_dims(const char *who, const MarlnavPolicyDims *d)
 {
-    if (d->num_parallel < 1)
-        return failf(MARLNAV_EINVAL, "%s: num_parallel=%lld < 1", who, (long long)d->num_parallel);
-    if (d->num_agents < 2 || d->num_agents > kMaxAgentsP)
-        return failf(MARLNAV_EINVAL, "%s: num_agents=%d outside [2, %d]", who, d->num_agents,
-                     kMaxAgentsP);
-    if (d->hidden_size < 1 || d->hidden_size > kMaxHidden)
-        return failf(MARLNAV_EINVAL, "%s: hidden_size=%d outside [1, %d]", who, d->hidden_size,
-                     kMaxHidden);
-    // D = 2 + 2 O + 2 (A - 1) for an observed obstacle count O in [1, 256]
-    const int twoO = d->obs_dim - 2 * d->num_agents;
-    if (twoO < 2 || (twoO & 1) || twoO > 2 * kMaxObstP)
-        return failf(MARLNAV_EINVAL,
-                     "%s: obs_dim=%d is not 2 + 2*O + 2*(A-1) for num_agents=%d and an O in "
-                     "[1, %d]", who, d->obs_dim, d->num_agents, kMaxObstP);
+    if (int rc = check_policy_shape(who, d->num_parallel, d->num_agents, d->obs_dim,
+                                    d->hidden_size))
+        return rc;
     if (d->reserved != 0 || d->env_offset < 0)
         return failf(MARLNAV_EINVAL, "%s: reserved=%d must be 0 and env_offset=%lld >= 0", who,
                      d->reserved, (long long)d->env_offset);
@@ -504,11 +378,9 @@ int launch_actor(const MarlnavPolicyDims *d, const MarlnavPolicyBuffers *b, int 
         for (const ActorVariant &c : kVariants)
             if (c.D == a.D) v = &c;
     const int64_t nblk = (a.rows + kRowsPerBlock - 1) / kRowsPerBlock;
-    const size_t lds = sizeof(float) * lds_floats(a.D);
+    const size_t lds = sizeof(float) * collapse_lds_floats(a.D);
     hipLaunchKernelGGL(v->fn[mode], dim3((unsigned)nblk), dim3(kThreads), lds, stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 }  // namespace
@@ -642,11 +514,10 @@ int marlnav_rollout_evaluate(const MarlnavDims *dims, const MarlnavParams *param
     hipStream_t s = (hipStream_t)stream;
     if (int rc = marlnav_observe(dims, params, env->states, env->obstacles, env->target, env->obs,
                                  stream))
-        return fail_step(rc, 0, "marlnav_observe");
+        return fail_step(who, rc, 0, "marlnav_observe");
     hipLaunchKernelGGL(eval_obs_norm_kernel, dim3((unsigned)norm_blocks), dim3(kThreads), 0, s,
                        env->obs, env->norm_mean, env->norm_scale, row_obs, D, eval->obs_norm_a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_launch(0, "normaliser", e);
+    if (int rc = launch_status()) return fail_step(who, rc, 0, "normaliser");
 
     // ---- the tracker's start and trace row 0
     TrackArgs ta;
@@ -661,8 +532,7 @@ int marlnav_rollout_evaluate(const MarlnavDims *dims, const MarlnavParams *param
     ta.S = S;
     const dim3 track_grid((unsigned)(env_blocks + (trace ? 1 : 0)));
     hipLaunchKernelGGL(eval_init_kernel, track_grid, dim3(kThreads), 0, s, ta);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_launch(0, "tracker start", e);
+    if (int rc = launch_status()) return fail_step(who, rc, 0, "tracker start");
 
     // ---- the steps (animation.py:40-71)
     MarlnavPolicyBuffers pb = *policy;
@@ -678,10 +548,10 @@ int marlnav_rollout_evaluate(const MarlnavDims *dims, const MarlnavParams *param
     for (int64_t t = 0; t < T; ++t) {
         pb.obs_norm = (t & 1) ? eval->obs_norm_b : eval->obs_norm_a;
         if (int rc = launch_actor(pdims, &pb, mode, policy_seed, policy_step_idx0 + (uint64_t)t, s))
-            return fail_step(rc, t, "marlnav_actor_act");
+            return fail_step(who, rc, t, "marlnav_actor_act");
         sb.obs_norm = (t & 1) ? eval->obs_norm_a : eval->obs_norm_b;
         if (int rc = marlnav_step(dims, params, &sb, env_step_idx0 + (uint64_t)t, stream))
-            return fail_step(rc, t, "marlnav_step");
+            return fail_step(who, rc, t, "marlnav_step");
         if (sb.states_out) {  // the step wrote the new states there: current from here on
             float *cur = sb.states_out;
             sb.states_out = sb.states;
@@ -690,13 +560,11 @@ int marlnav_rollout_evaluate(const MarlnavDims *dims, const MarlnavParams *param
         ta.states = sb.states;
         ta.row = t + 1;
         hipLaunchKernelGGL(eval_track_kernel, track_grid, dim3(kThreads), 0, s, ta);
-        e = hipGetLastError();
-        if (e != hipSuccess) return fail_launch(t, "tracker", e);
+        if (int rc = launch_status()) return fail_step(who, rc, t, "tracker");
     }
 
     hipLaunchKernelGGL(eval_summary_kernel, dim3(1), dim3(kSummaryThreads), 0, s, *eval, P);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail_launch(T - 1, "totals after it", e);
+    if (int rc = launch_status()) return fail_step(who, rc, T - 1, "totals after it");
     return 0;
 }
 

@@ -45,9 +45,16 @@
 // native_key() hashes blk * odd constant, a bijection, so under one seed and
 // step the two domains never share a key.
 //
-// Built with -ffp-contract=off: every FMA below is explicit.
+// The collapse, the row chains, the sampling tail and the critic sum are the
+// functions of policy_forward.h, which actor_kernel (marlnav_eval.hip) shares
+// too (all but the collapse, written out there); policy_kernel and
+// critic_values_kernel are their own thread-to-row mappings and barriers
+// around them.
+//
+// Built with -ffp-contract=off: every FMA is explicit.
 #include <hip/hip_runtime.h>
 
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -57,22 +64,13 @@ __attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const 
 
 namespace {
 
-#include "device_rng.h"
+#include "policy_forward.h"
+#include "host_util.h"
 
-constexpr int kThreads = 256;
 constexpr int kEnvsPerBlock = 64;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxAgentsP = 64, kMaxObstP = 256, kMaxHidden = 512;
-constexpr int kMaxD = 2 * kMaxAgentsP + 2 * kMaxObstP;  // 640
-// dynamic LDS floats of a block: Weff and its kWaves partials (4 D each),
-// beff and its partials, the critic partials
-constexpr size_t lds_floats(int D)
-{
-    return (size_t)(1 + kWaves) * 4 * D + 4 + 4 * kWaves + kWaves * kEnvsPerBlock;
-}
+// dynamic LDS floats of a block: the collapse, then the critic partials
+constexpr size_t lds_floats(int D) { return collapse_lds_floats(D) + kWaves * kEnvsPerBlock; }
 static_assert(lds_floats(kMaxD) * sizeof(float) <= 64 * 1024, "LDS of the widest row");
-constexpr uint32_t kPolicyBlock = 0x80000000u;           // Philox block-index domain
-constexpr float kLog2Pi = 1.8378770664093453f;
 
 struct PolicyArgs {
     MarlnavPolicyBuffers b;
@@ -82,188 +80,42 @@ struct PolicyArgs {
     uint64_t step;
 };
 
-// N consecutive floats at p into registers with the widest loads N allows
-// (the caller guarantees p is 16-byte aligned when N % 4 == 0, 8-byte when
-// N % 2 == 0: obs is 16-byte aligned and rows are N floats apart)
-template <int N>
-__device__ __forceinline__ void load_row(const float *__restrict__ p, float (&x)[N])
-{
-    if constexpr (N % 4 == 0) {
-#pragma unroll
-        for (int i = 0; i < N / 4; ++i) {
-            const float4 v = reinterpret_cast<const float4 *>(p)[i];
-            x[4 * i] = v.x, x[4 * i + 1] = v.y, x[4 * i + 2] = v.z, x[4 * i + 3] = v.w;
-        }
-    } else if constexpr (N % 2 == 0) {
-#pragma unroll
-        for (int i = 0; i < N / 2; ++i) {
-            const float2 v = reinterpret_cast<const float2 *>(p)[i];
-            x[2 * i] = v.x, x[2 * i + 1] = v.y;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; ++i) x[i] = p[i];
-    }
-}
-
-__device__ __forceinline__ float relu_t(float a) { return a < 0.0f ? 0.0f : a; }  // NaN stays
-
-// torch.nn.functional.softplus (beta 1, threshold 20)
-__device__ __forceinline__ float softplus_t(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
-
-// two standard normals of global agent row gid at step s: Box-Muller on the
-// two words of one Philox block, u1 in (0, 1], u2 in [0, 1) on the 24-bit grid
-__device__ __forceinline__ void policy_normals(uint64_t seed, uint64_t gid, uint64_t s, float &z0,
-                                               float &z1)
-{
-    uint32_t r0, r1;
-    native_block(seed, kPolicyBlock, gid, s, r0, r1);
-    const float u1 = (float)((r0 >> 8) + 1u) * 0x1.0p-24f;
-    const float u2 = native_u24(r1);
-    const float rad = sqrtf(-2.0f * logf(u1));
-    // v_sin_f32 / v_cos_f32 take the angle in revolutions: no range reduction
-    z0 = rad * __builtin_amdgcn_cosf(u2);
-    z1 = rad * __builtin_amdgcn_sinf(u2);
-}
-
 // A_T, D_T: compiled shape (0: run-time A, D; inputs read from memory as used)
 template <int A_T, int D_T>
 __global__ void __launch_bounds__(kThreads) policy_kernel(PolicyArgs g)
 {
+    static_assert((A_T != 0) == (D_T != 0), "a compiled shape fixes both");
     const int A = A_T ? A_T : g.A;
     const int D = D_T ? D_T : g.D;
-    const int H = g.H;
-    const int AD = A * D;
     const int64_t P = g.P;
     const float *__restrict__ obs = g.b.obs_norm;
 
-    // LDS, all in the dynamic region (16-byte aligned base and offsets):
-    // Weff as [k][4], the four waves' partial Weff, beff, its partials, the
-    // critic partials
+    // LDS, all in the dynamic region: the collapse, then the critic partials
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
-    float *s_w = s_dyn;
-    float *s_wp = s_w + 4 * D;
-    float *s_b = s_wp + kWaves * 4 * D;
-    float *s_bp = s_b + 4;
-    float *s_part = s_bp + 4 * kWaves;
+    float *s_part = lds_bp(s_dyn, D) + 4 * kWaves;
 
     const int t = threadIdx.x;
     const int q = __builtin_amdgcn_readfirstlane(t >> 6);  // wave of the block
     const int lane = t & 63;
-    // wave q's share of the hidden units, in the collapse and in the critic
-    const int Hq = (H + kWaves - 1) / kWaves;
-    const int j0 = q * Hq, j1 = (j0 + Hq < H) ? j0 + Hq : H;
+    int j0, j1;
+    wave_share(g.H, q, j0, j1);
 
-    // ---- collapse the actor: Weff[r][k] = sum_j head_r[j] W1[j][k], each
-    // wave summing its hidden units (the loads of a group of 8 issued before
-    // the first FMA: a rolled loop paid one memory round trip per unit)
+    collapse_partials<D_T>(g.b.actor_fc1_w, g.b.actor_fc1_b, g.b.actor_mu_w, g.b.actor_std_w, D,
+                           g.H, q, lane, j0, j1, s_dyn);
+    // critic: wave q sums hidden units [j0, j1) for the block's 64 envs
     {
-        const float *__restrict__ w1 = g.b.actor_fc1_w;
-        const float *__restrict__ b1 = g.b.actor_fc1_b;
-        // rows 0..4D-1: Weff[r][k] with r = idx / D, k = idx % D; then four
-        // rows for beff's sums over fc1.bias (the same code with b1 for W1)
-        for (int idx = lane; idx < 4 * D + 4; idx += 64) {
-            const bool bias = idx >= 4 * D;
-            const int r = bias ? idx - 4 * D : idx / D;
-            const int k = bias ? 0 : idx - r * D;
-            const float *__restrict__ head = (r < 2 ? g.b.actor_mu_w : g.b.actor_std_w) + (r & 1) * H;
-            const float *__restrict__ col = bias ? b1 : w1 + k;
-            const int64_t stride = bias ? 1 : D;
-            float acc = 0.0f;
-            for (int j = j0; j < j1; j += 8) {
-                float a[8], b[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int jj = j + i < j1 ? j + i : j1 - 1;  // a short last group repeats a unit
-                    a[i] = head[jj];
-                    b[i] = col[jj * stride];
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    if (j + i < j1) acc = __builtin_fmaf(a[i], b[i], acc);
-            }
-            if (bias)
-                s_bp[4 * q + r] = acc;
-            else
-                s_wp[q * 4 * D + 4 * k + r] = acc;
-        }
-    }
-
-    // ---- critic: wave q sums hidden units [j0, j1) for the block's 64 envs
-    {
-        const int e = lane;
-        const int64_t env_raw = (int64_t)blockIdx.x * kEnvsPerBlock + e;
+        const int64_t env_raw = (int64_t)blockIdx.x * kEnvsPerBlock + lane;
         const int64_t env = env_raw < P ? env_raw : P - 1;  // lanes past the end stay in bounds
-        const float *__restrict__ xe = obs + env * AD;
-        const float *__restrict__ wc = g.b.critic_fc1_w;
-        const float *__restrict__ bc = g.b.critic_fc1_b;
-        const float *__restrict__ w2 = g.b.critic_fc2_w;
-        float part = 0.0f;
-        if constexpr (A_T != 0 && D_T != 0) {
-            float x[A_T * D_T];
-            load_row<A_T * D_T>(xe, x);
-            for (int j = j0; j < j1; j += 4) {
-                float acc[4];
-                const float *wr[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int jj = j + i < j1 ? j + i : j1 - 1;  // a short last group repeats a row
-                    acc[i] = bc[jj];
-                    wr[i] = wc + (int64_t)jj * (A_T * D_T);
-                }
-#pragma unroll
-                for (int k = 0; k < A_T * D_T; ++k)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[i] = __builtin_fmaf(wr[i][k], x[k], acc[i]);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (j + i < j1) part = __builtin_fmaf(w2[j + i], relu_t(acc[i]), part);
-            }
-        } else {
-            for (int j = j0; j < j1; j += 4) {
-                float acc[4];
-                const float *wr[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int jj = j + i < j1 ? j + i : j1 - 1;
-                    acc[i] = bc[jj];
-                    wr[i] = wc + (int64_t)jj * AD;
-                }
-                for (int k = 0; k < AD; ++k) {
-                    const float xv = xe[k];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[i] = __builtin_fmaf(wr[i][k], xv, acc[i]);
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (j + i < j1) part = __builtin_fmaf(w2[j + i], relu_t(acc[i]), part);
-            }
-        }
-        s_part[q * kEnvsPerBlock + e] = part;
+        s_part[q * kEnvsPerBlock + lane] =
+            critic_partial<A_T * D_T>(obs + env * (A * D), g.b.critic_fc1_w, g.b.critic_fc1_b,
+                                      g.b.critic_fc2_w, A * D, j0, j1);
     }
     __syncthreads();  // the waves' partial Weff, beff and critic sums are in LDS
 
-    // the partial sums, added in wave order
-    for (int idx = t; idx < 4 * D; idx += kThreads) {
-        float v = s_wp[idx];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) v += s_wp[w * 4 * D + idx];
-        s_w[idx] = v;
-    }
-    if (t < 4) {
-        float v = s_bp[t];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) v += s_bp[4 * w + t];
-        s_b[t] = (t < 2 ? g.b.actor_mu_b : g.b.actor_std_b)[t & 1] + v;
-    }
+    collapse_sum(g.b.actor_mu_b, g.b.actor_std_b, D, t, s_dyn);
     if (t < kEnvsPerBlock) {
         const int64_t env = (int64_t)blockIdx.x * kEnvsPerBlock + t;
-        if (env < P) {
-            float v = s_part[t];
-#pragma unroll
-            for (int w = 1; w < kWaves; ++w) v += s_part[w * kEnvsPerBlock + t];
-            g.b.values[env] = v + g.b.critic_fc2_b[0];
-        }
+        if (env < P) g.b.values[env] = critic_total(s_part, kEnvsPerBlock, t, g.b.critic_fc2_b);
     }
     __syncthreads();  // Weff and beff are in LDS
 
@@ -271,49 +123,16 @@ __global__ void __launch_bounds__(kThreads) policy_kernel(PolicyArgs g)
     const int64_t row0 = (int64_t)blockIdx.x * kEnvsPerBlock * A;
     const int64_t rows_total = P * A;
     const int rows_block = kEnvsPerBlock * A;
-    const float4 be = *reinterpret_cast<const float4 *>(s_b);
+    const float4 be = *reinterpret_cast<const float4 *>(lds_b(s_dyn, D));
     for (int r = t; r < rows_block; r += kThreads) {
         const int64_t row = row0 + r;
         if (row >= rows_total) break;
-        const float *__restrict__ xr = obs + row * D;
-        float p0 = be.x, p1 = be.y, p2 = be.z, p3 = be.w;
-        if constexpr (D_T != 0) {
-            float x[D_T];
-            load_row<D_T>(xr, x);
-#pragma unroll
-            for (int k = 0; k < D_T; ++k) {
-                const float4 w = *reinterpret_cast<const float4 *>(s_w + 4 * k);
-                p0 = __builtin_fmaf(w.x, x[k], p0);
-                p1 = __builtin_fmaf(w.y, x[k], p1);
-                p2 = __builtin_fmaf(w.z, x[k], p2);
-                p3 = __builtin_fmaf(w.w, x[k], p3);
-            }
-        } else {
-            for (int k = 0; k < D; ++k) {
-                const float4 w = *reinterpret_cast<const float4 *>(s_w + 4 * k);
-                const float xv = xr[k];
-                p0 = __builtin_fmaf(w.x, xv, p0);
-                p1 = __builtin_fmaf(w.y, xv, p1);
-                p2 = __builtin_fmaf(w.z, xv, p2);
-                p3 = __builtin_fmaf(w.w, xv, p3);
-            }
-        }
-        const float mu0 = tanhf(p0), mu1 = tanhf(p1);
-        const float v0 = softplus_t(p2), v1 = softplus_t(p3);
+        const float4 p = row_chains<D_T, true>(obs + row * D, D, be, s_dyn);
+        const float mu0 = tanhf(p.x), mu1 = tanhf(p.y);
+        const float v0 = softplus_t(p.z), v1 = softplus_t(p.w);
         float e0, e1;
-        if (g.b.eps) {
-            e0 = g.b.eps[2 * row];
-            e1 = g.b.eps[2 * row + 1];
-        } else {
-            policy_normals(g.seed, (uint64_t)(g.env_offset * A + row), g.step, e0, e1);
-        }
-        if (g.b.eps_out) {
-            g.b.eps_out[2 * row] = e0;
-            g.b.eps_out[2 * row + 1] = e1;
-        }
-        // loc + scale_tril @ eps: the product and the sum round separately
-        g.b.actions[2 * row] = mu0 + sqrtf(v0) * e0;
-        g.b.actions[2 * row + 1] = mu1 + sqrtf(v1) * e1;
+        sample_action(g.b.eps, g.b.eps_out, g.b.actions, mu0, mu1, v0, v1, row, g.seed,
+                      (uint64_t)(g.env_offset * A + row), g.step, e0, e1);
         const float m = __builtin_fmaf(e1, e1, e0 * e0);
         const float ld = logf(v0) + logf(v1);
         g.b.log_probs[row] = __builtin_fmaf(-0.5f, m, __builtin_fmaf(-0.5f, ld, -kLog2Pi));
@@ -321,133 +140,90 @@ __global__ void __launch_bounds__(kThreads) policy_kernel(PolicyArgs g)
 }
 
 // The critic of policy_kernel alone (marlnav_critic_values):
-// the same blocks of 64 envs, the same wave shares of the hidden units, the
-// same FMA chains and the same wave-order sum, so values[env] carries the bits
+// the same blocks of 64 envs, the same wave shares of the hidden units and the
+// same critic_partial / critic_total calls, so values[env] carries the bits
 // policy_kernel stores for the same observations and weights. It is a kernel
-// of its own, not a mode of policy_kernel, and the critic sum is restated, not
-// shared: a function called from both changed policy_kernel's compiled code,
-// and the rollout's hot launch keeps its code. The bit
-// identity is held by tests/test_gae_gpu.py. Reads no actor tensor and draws
+// of its own, not a mode of policy_kernel. Reads no actor tensor and draws
 // nothing.
 template <int A_T, int D_T>
 __global__ void __launch_bounds__(kThreads) critic_values_kernel(PolicyArgs g)
 {
     const int AD = (A_T ? A_T : g.A) * (D_T ? D_T : g.D);
-    const int H = g.H;
     const int64_t P = g.P;
     __shared__ float s_part[kWaves * kEnvsPerBlock];
 
     const int t = threadIdx.x;
     const int q = __builtin_amdgcn_readfirstlane(t >> 6);
     const int e = t & 63;
-    const int Hq = (H + kWaves - 1) / kWaves;
-    const int j0 = q * Hq, j1 = (j0 + Hq < H) ? j0 + Hq : H;
+    int j0, j1;
+    wave_share(g.H, q, j0, j1);
 
     const int64_t env_raw = (int64_t)blockIdx.x * kEnvsPerBlock + e;
     const int64_t env = env_raw < P ? env_raw : P - 1;  // lanes past the end stay in bounds
-    const float *__restrict__ xe = g.b.obs_norm + env * AD;
-    const float *__restrict__ wc = g.b.critic_fc1_w;
-    const float *__restrict__ bc = g.b.critic_fc1_b;
-    const float *__restrict__ w2 = g.b.critic_fc2_w;
-    float part = 0.0f;
-    if constexpr (A_T != 0 && D_T != 0) {
-        float x[A_T * D_T];
-        load_row<A_T * D_T>(xe, x);
-        for (int j = j0; j < j1; j += 4) {
-            float acc[4];
-            const float *wr[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int jj = j + i < j1 ? j + i : j1 - 1;  // a short last group repeats a row
-                acc[i] = bc[jj];
-                wr[i] = wc + (int64_t)jj * (A_T * D_T);
-            }
-#pragma unroll
-            for (int k = 0; k < A_T * D_T; ++k)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = __builtin_fmaf(wr[i][k], x[k], acc[i]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (j + i < j1) part = __builtin_fmaf(w2[j + i], relu_t(acc[i]), part);
-        }
-    } else {
-        for (int j = j0; j < j1; j += 4) {
-            float acc[4];
-            const float *wr[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int jj = j + i < j1 ? j + i : j1 - 1;
-                acc[i] = bc[jj];
-                wr[i] = wc + (int64_t)jj * AD;
-            }
-            for (int k = 0; k < AD; ++k) {
-                const float xv = xe[k];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = __builtin_fmaf(wr[i][k], xv, acc[i]);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (j + i < j1) part = __builtin_fmaf(w2[j + i], relu_t(acc[i]), part);
-        }
-    }
-    s_part[q * kEnvsPerBlock + e] = part;
+    s_part[q * kEnvsPerBlock + e] =
+        critic_partial<A_T * D_T>(g.b.obs_norm + env * AD, g.b.critic_fc1_w, g.b.critic_fc1_b,
+                                  g.b.critic_fc2_w, AD, j0, j1);
     __syncthreads();
-    if (t < kEnvsPerBlock && env_raw < P) {
-        float v = s_part[t];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) v += s_part[w * kEnvsPerBlock + t];
-        g.b.values[env_raw] = v + g.b.critic_fc2_b[0];
-    }
+    if (t < kEnvsPerBlock && env_raw < P)
+        g.b.values[env_raw] = critic_total(s_part, kEnvsPerBlock, t, g.b.critic_fc2_b);
 }
 
 using PolicyFn = void (*)(PolicyArgs);
 
+// compiled shapes: 3 agents x 3 and x 8 obstacles (the benchmark's), then the
+// generic kernels
 struct PolicyVariant {
     int A, D;
-    PolicyFn fn;
+    PolicyFn act, values;
 };
-
-// compiled shapes: 3 agents x 3 and x 8 obstacles (the benchmark's)
 const PolicyVariant kVariants[] = {
-    {3, 12, policy_kernel<3, 12>},
-    {3, 22, policy_kernel<3, 22>},
+    {3, 12, policy_kernel<3, 12>, critic_values_kernel<3, 12>},
+    {3, 22, policy_kernel<3, 22>, critic_values_kernel<3, 22>},
 };
-const PolicyVariant kCriticVariants[] = {
-    {3, 12, critic_values_kernel<3, 12>},
-    {3, 22, critic_values_kernel<3, 22>},
-};
-
-int failf(int code, const char *fmt, long long a, long long b, long long c)
-{
-    char msg[256];
-    snprintf(msg, sizeof(msg), fmt, a, b, c);
-    return marlnav_internal_fail(code, msg);
-}
+const PolicyVariant kGeneric = {0, 0, policy_kernel<0, 0>, critic_values_kernel<0, 0>};
 
 // the dims checks of both entry points; 0 or the failing code
 int check_dims(const MarlnavPolicyDims *d, const MarlnavPolicyBuffers *b)
 {
     if (!d || !b) return marlnav_internal_fail(MARLNAV_EINVAL, "policy dims/buffers is NULL");
-    if (d->num_parallel < 1)
-        return failf(MARLNAV_EINVAL, "policy: num_parallel=%lld < 1", d->num_parallel, 0, 0);
-    if (d->num_agents < 2 || d->num_agents > kMaxAgentsP)
-        return failf(MARLNAV_EINVAL, "policy: num_agents=%lld outside [2, %lld]", d->num_agents,
-                     kMaxAgentsP, 0);
-    if (d->hidden_size < 1 || d->hidden_size > kMaxHidden)
-        return failf(MARLNAV_EINVAL, "policy: hidden_size=%lld outside [1, %lld]", d->hidden_size,
-                     kMaxHidden, 0);
-    {
-        // D = 2 + 2 O + 2 (A - 1) for an observed obstacle count O in [1, 256]
-        const int twoO = d->obs_dim - 2 * d->num_agents;
-        if (twoO < 2 || (twoO & 1) || twoO > 2 * kMaxObstP)
-            return failf(MARLNAV_EINVAL,
-                         "policy: obs_dim=%lld is not 2 + 2*O + 2*(A-1) for num_agents=%lld and "
-                         "an O in [1, %lld]",
-                         d->obs_dim, d->num_agents, kMaxObstP);
-    }
+    if (int rc = check_policy_shape("policy", d->num_parallel, d->num_agents, d->obs_dim,
+                                    d->hidden_size))
+        return rc;
     if (d->reserved != 0 || d->env_offset < 0)
-        return failf(MARLNAV_EINVAL, "policy: reserved=%lld must be 0 and env_offset=%lld >= 0",
-                     d->reserved, d->env_offset, 0);
+        return failf(MARLNAV_EINVAL, "policy: reserved=%d must be 0 and env_offset=%lld >= 0",
+                     d->reserved, (long long)d->env_offset);
+    return 0;
+}
+
+// what a launch of either entry point needs (dims checked, buffers given)
+struct PolicyLaunch {
+    PolicyArgs args;
+    const PolicyVariant *variant;
+    dim3 grid;
+};
+
+// 0 and the launch filled in, or the failing code
+int plan_launch(const MarlnavPolicyDims *d, const MarlnavPolicyBuffers *b, uint64_t seed,
+                uint64_t step, PolicyLaunch &l)
+{
+    const int64_t nblk = (d->num_parallel + kEnvsPerBlock - 1) / kEnvsPerBlock;
+    if (nblk > 0x7fffffff)
+        return failf(MARLNAV_EINVAL, "policy: num_parallel=%lld too large",
+                     (long long)d->num_parallel);
+    l.args.b = *b;
+    l.args.P = d->num_parallel;
+    l.args.env_offset = d->env_offset;
+    l.args.A = d->num_agents;
+    l.args.D = d->obs_dim;
+    l.args.H = d->hidden_size;
+    l.args.seed = seed;
+    l.args.step = step;
+    l.grid = dim3((unsigned)nblk);
+    l.variant = &kGeneric;
+    // the compiled shapes load rows as 16- / 8-byte vectors
+    if ((reinterpret_cast<uintptr_t>(b->obs_norm) & 15u) == 0)
+        for (const PolicyVariant &v : kVariants)
+            if (v.A == l.args.A && v.D == l.args.D) l.variant = &v;
     return 0;
 }
 
@@ -461,29 +237,11 @@ extern "C" int marlnav_policy_act(const MarlnavPolicyDims *d, const MarlnavPolic
         !b->actor_std_w || !b->actor_std_b || !b->critic_fc1_w || !b->critic_fc1_b ||
         !b->critic_fc2_w || !b->critic_fc2_b || !b->actions || !b->log_probs || !b->values)
         return marlnav_internal_fail(MARLNAV_EINVAL, "a required policy buffer is NULL");
-    const int64_t nblk = (d->num_parallel + kEnvsPerBlock - 1) / kEnvsPerBlock;
-    if (nblk > 0x7fffffff)
-        return failf(MARLNAV_EINVAL, "policy: num_parallel=%lld too large", d->num_parallel, 0, 0);
-
-    PolicyArgs args;
-    args.b = *b;
-    args.P = d->num_parallel;
-    args.env_offset = d->env_offset;
-    args.A = d->num_agents;
-    args.D = d->obs_dim;
-    args.H = d->hidden_size;
-    args.seed = native_seed_mix(policy_seed);
-    args.step = step_idx;
-    PolicyFn fn = policy_kernel<0, 0>;
-    // the compiled shapes load rows as 16- / 8-byte vectors
-    if ((reinterpret_cast<uintptr_t>(b->obs_norm) & 15u) == 0)
-        for (const PolicyVariant &v : kVariants)
-            if (v.A == args.A && v.D == args.D) fn = v.fn;
-    const size_t lds = sizeof(float) * lds_floats(args.D);
-    hipLaunchKernelGGL(fn, dim3((unsigned)nblk), dim3(kThreads), lds, (hipStream_t)stream, args);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
-    return 0;
+    PolicyLaunch l;
+    if (int rc = plan_launch(d, b, native_seed_mix(policy_seed), step_idx, l)) return rc;
+    const size_t lds = sizeof(float) * lds_floats(l.args.D);
+    hipLaunchKernelGGL(l.variant->act, l.grid, dim3(kThreads), lds, (hipStream_t)stream, l.args);
+    return launch_status();
 }
 
 extern "C" int marlnav_critic_values(const MarlnavPolicyDims *d, const MarlnavPolicyBuffers *b,
@@ -494,25 +252,8 @@ extern "C" int marlnav_critic_values(const MarlnavPolicyDims *d, const MarlnavPo
         !b->critic_fc2_b || !b->values)
         return marlnav_internal_fail(
             MARLNAV_EINVAL, "critic values: a required buffer (obs_norm, critic_*, values) is NULL");
-    const int64_t nblk = (d->num_parallel + kEnvsPerBlock - 1) / kEnvsPerBlock;
-    if (nblk > 0x7fffffff)
-        return failf(MARLNAV_EINVAL, "policy: num_parallel=%lld too large", d->num_parallel, 0, 0);
-
-    PolicyArgs args;
-    args.b = *b;
-    args.P = d->num_parallel;
-    args.env_offset = d->env_offset;
-    args.A = d->num_agents;
-    args.D = d->obs_dim;
-    args.H = d->hidden_size;
-    args.seed = 0;
-    args.step = 0;
-    PolicyFn fn = critic_values_kernel<0, 0>;
-    if ((reinterpret_cast<uintptr_t>(b->obs_norm) & 15u) == 0)
-        for (const PolicyVariant &v : kCriticVariants)
-            if (v.A == args.A && v.D == args.D) fn = v.fn;
-    hipLaunchKernelGGL(fn, dim3((unsigned)nblk), dim3(kThreads), 0, (hipStream_t)stream, args);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
-    return 0;
+    PolicyLaunch l;
+    if (int rc = plan_launch(d, b, 0, 0, l)) return rc;
+    hipLaunchKernelGGL(l.variant->values, l.grid, dim3(kThreads), 0, (hipStream_t)stream, l.args);
+    return launch_status();
 }

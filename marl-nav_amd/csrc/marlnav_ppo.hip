@@ -47,6 +47,7 @@
 // dims only. Built with -ffp-contract=off: every FMA below is explicit.
 #include <hip/hip_runtime.h>
 
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -57,11 +58,11 @@ __attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const 
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxAgentsP = 64, kMaxObstP = 256, kMaxHidden = 512;
-constexpr int kMaxD = 2 * kMaxAgentsP + 2 * kMaxObstP;  // 640
-constexpr float kLog2Pi = 1.8378770664093453f;
+// the block shape, the policy's limits, kLog2Pi and relu_t; block_sum; failf,
+// launch_status and the shape check
+#include "policy_forward.h"
+#include "block_sum.h"
+#include "host_util.h"
 
 // ---- actor tiling
 constexpr int kActorTile = kThreads;       // rows per tile
@@ -145,23 +146,6 @@ template <class T>
 __device__ __forceinline__ const T &only(const T &x)
 {
     return x;
-}
-
-__device__ __forceinline__ float relu_t(float a) { return a < 0.0f ? 0.0f : a; }  // NaN stays
-
-// wave partial sums (fixed shuffle tree), then the waves in order; valid in
-// thread 0. sh: kWaves doubles of LDS.
-__device__ __forceinline__ double block_sum(double v, double *sh)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < kWaves; ++i) t += sh[i];
-    __syncthreads();
-    return t;
 }
 
 // p[0] + p[stride] + ... (n terms) in that order, the loads of eight terms
@@ -820,40 +804,23 @@ __global__ void __launch_bounds__(kThreads) critic_finish(PpoArgs g, X... x)
 
 
 // ---- host side
-int failf(int code, const char *fmt, long long a, long long b, long long c)
-{
-    char msg[256];
-    snprintf(msg, sizeof(msg), fmt, a, b, c);
-    return marlnav_internal_fail(code, msg);
-}
-
 int check_dims(const MarlnavPpoDims *d)
 {
     if (!d) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo dims is NULL");
-    if (d->num_parallel < 1)
-        return failf(MARLNAV_EINVAL, "ppo: num_parallel=%lld < 1", d->num_parallel, 0, 0);
-    if (d->num_steps < 1)
-        return failf(MARLNAV_EINVAL, "ppo: num_steps=%lld < 1", d->num_steps, 0, 0);
-    if (d->num_agents < 2 || d->num_agents > kMaxAgentsP)
-        return failf(MARLNAV_EINVAL, "ppo: num_agents=%lld outside [2, %lld]", d->num_agents,
-                     kMaxAgentsP, 0);
-    if (d->hidden_size < 1 || d->hidden_size > kMaxHidden)
-        return failf(MARLNAV_EINVAL, "ppo: hidden_size=%lld outside [1, %lld]", d->hidden_size,
-                     kMaxHidden, 0);
-    const int twoO = d->obs_dim - 2 * d->num_agents;
-    if (twoO < 2 || (twoO & 1) || twoO > 2 * kMaxObstP)
-        return failf(MARLNAV_EINVAL,
-                     "ppo: obs_dim=%lld is not 2 + 2*O + 2*(A-1) for num_agents=%lld and an O in "
-                     "[1, %lld]",
-                     d->obs_dim, d->num_agents, kMaxObstP);
-    if (d->reserved != 0) return failf(MARLNAV_EINVAL, "ppo: reserved=%lld must be 0", d->reserved, 0, 0);
+    // (num_steps is reported after num_parallel and before the rest of the shape)
+    if (d->num_parallel >= 1 && d->num_steps < 1)
+        return failf(MARLNAV_EINVAL, "ppo: num_steps=%lld < 1", (long long)d->num_steps);
+    if (int rc = check_policy_shape("ppo", d->num_parallel, d->num_agents, d->obs_dim,
+                                    d->hidden_size))
+        return rc;
+    if (d->reserved != 0) return failf(MARLNAV_EINVAL, "ppo: reserved=%d must be 0", d->reserved);
     if (d->num_steps > ((int64_t)1 << 40) / d->num_parallel / d->num_agents)
         return failf(MARLNAV_EINVAL, "ppo: num_steps=%lld x num_parallel=%lld rows are too many",
-                     d->num_steps, d->num_parallel, 0);
+                     (long long)d->num_steps, (long long)d->num_parallel);
     if (d->num_steps * d->num_parallel < 2)
         return failf(MARLNAV_EINVAL,
                      "ppo: num_steps=%lld x num_parallel=%lld gives fewer than 2 env rows",
-                     d->num_steps, d->num_parallel, 0);
+                     (long long)d->num_steps, (long long)d->num_parallel);
     return 0;
 }
 
@@ -950,8 +917,8 @@ int check_mode(int advantage_mode)
 {
     if (advantage_mode != MARLNAV_ADVANTAGE_REFERENCE && advantage_mode != MARLNAV_ADVANTAGE_ENV)
         return failf(MARLNAV_EINVAL,
-                     "ppo: advantage_mode=%lld must be MARLNAV_ADVANTAGE_REFERENCE or _ENV",
-                     advantage_mode, 0, 0);
+                     "ppo: advantage_mode=%d must be MARLNAV_ADVANTAGE_REFERENCE or _ENV",
+                     advantage_mode);
     return 0;
 }
 
@@ -999,13 +966,6 @@ int check_critic_bufs(const MarlnavPpoBuffers *b)
     PPO_NEED(work);
     if (reinterpret_cast<uintptr_t>(b->obs) & 7u)
         return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer obs must be 8-byte aligned");
-    return 0;
-}
-
-int launch_status()
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
     return 0;
 }
 

@@ -31,20 +31,10 @@ __attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const 
 namespace {
 
 constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
 
-__device__ __forceinline__ double block_sum(double v, double *sh)
-{
-    // wave partial sums (fixed shuffle tree), then the 4 waves in order
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < kThreads / 64; ++i) t += sh[i];
-    __syncthreads();
-    return t;  // valid in thread 0
-}
+#include "block_sum.h"
+#include "host_util.h"
 
 // G_t = done_t ? 0 : r_t + gamma * G_{t+1}  (models.py:133-137)
 __global__ void __launch_bounds__(kThreads) returns_kernel(const float *__restrict__ rew,
@@ -53,7 +43,7 @@ __global__ void __launch_bounds__(kThreads) returns_kernel(const float *__restri
                                                             double *__restrict__ ret,
                                                             double *__restrict__ partial)
 {
-    __shared__ double sh[kThreads / 64];
+    __shared__ double sh[kWaves];
     const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     double s = 0.0;
     if (e < P) {
@@ -85,7 +75,7 @@ __global__ void __launch_bounds__(kThreads) gae_kernel(const float *__restrict__
                                                         double *__restrict__ vt,
                                                         double *__restrict__ partial)
 {
-    __shared__ double sh[kThreads / 64];
+    __shared__ double sh[kWaves];
     const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     double s = 0.0;
     if (e < P) {
@@ -112,7 +102,7 @@ __global__ void __launch_bounds__(kThreads) finish_kernel(const double *__restri
                                                            int64_t nb, int64_t n, int mode,
                                                            double *__restrict__ stats)
 {
-    __shared__ double sh[kThreads / 64];
+    __shared__ double sh[kWaves];
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < nb; i += kThreads) s += partial[i];
     const double t = block_sum(s, sh);
@@ -129,7 +119,7 @@ __global__ void __launch_bounds__(kThreads) sqdev_kernel(const double *__restric
                                                           const double *__restrict__ stats,
                                                           double *__restrict__ partial)
 {
-    __shared__ double sh[kThreads / 64];
+    __shared__ double sh[kWaves];
     const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     const double mean = stats[0];
     double s = 0.0;
@@ -210,31 +200,6 @@ __global__ void __launch_bounds__(kThreads) merge_flags_kernel(uint8_t *__restri
     done[i] = (done[i] | trunc[i]) != 0;
 }
 
-int failf(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-int failf(int code, const char *fmt, ...)
-{
-    char msg[400];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, sizeof(msg), fmt, ap);
-    va_end(ap);
-    return marlnav_internal_fail(code, msg);
-}
-
-// a launch of step t failed inside `what`: its message, with the step named
-int fail_step(int code, int64_t t, const char *what)
-{
-    char inner[256];
-    snprintf(inner, sizeof(inner), "%s", marlnav_last_error());
-    return failf(code, "marlnav_rollout_collect: step %lld, %s: %s", (long long)t, what, inner);
-}
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
 }  // namespace
 
 extern "C" {
@@ -260,9 +225,7 @@ int marlnav_discounted_returns(const float *rewards, const uint8_t *done, int64_
     hipLaunchKernelGGL(sqdev_kernel, grid, blk, 0, s, returns, T, P, stats, work + nb);
     hipLaunchKernelGGL(finish_kernel, dim3(1), blk, 0, s, work + nb, nb, T * P, 1, stats);
     hipLaunchKernelGGL(normalize_kernel, grid, blk, 0, s, returns, T, P, stats);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 int64_t marlnav_gae_work_size(int64_t P)
@@ -312,9 +275,7 @@ int marlnav_gae_advantages(const float *rewards, const uint8_t *done, const floa
     hipLaunchKernelGGL(sqdev_kernel, grid, blk, 0, s, advantages, T, P, stats, work + nb);
     hipLaunchKernelGGL(finish_kernel, dim3(1), blk, 0, s, work + nb, nb, T * P, 1, stats);
     hipLaunchKernelGGL(normalize_kernel, grid, blk, 0, s, advantages, T, P, stats);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return marlnav_internal_fail(MARLNAV_ELAUNCH, hipGetErrorString(e));
-    return 0;
+    return launch_status();
 }
 
 int marlnav_rollout_collect(const MarlnavDims *dims, const MarlnavParams *params,
@@ -325,6 +286,7 @@ int marlnav_rollout_collect(const MarlnavDims *dims, const MarlnavParams *params
                             void *stream)
 {
     constexpr int64_t kMaxSteps = (int64_t)1 << 20;
+    const char *who = "marlnav_rollout_collect";
     // ---- everything is checked before the first launch
     if (!dims || !params || !env || !pdims || !policy || !rollout)
         return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: %s is NULL",
@@ -351,9 +313,9 @@ int marlnav_rollout_collect(const MarlnavDims *dims, const MarlnavParams *params
         return failf(MARLNAV_EINVAL,
                      "marlnav_rollout_collect: policy env_offset=%lld, env %lld (equal and >= 0)",
                      (long long)pdims->env_offset, (long long)dims->env_offset);
-    if (pdims->hidden_size < 1 || pdims->hidden_size > 512)
+    if (pdims->hidden_size < 1 || pdims->hidden_size > kMaxHidden)
         return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: policy hidden_size=%d outside "
-                     "[1, 512]", pdims->hidden_size);
+                     "[1, %d]", pdims->hidden_size, kMaxHidden);
     if (pdims->reserved != 0)
         return failf(MARLNAV_EINVAL, "marlnav_rollout_collect: policy reserved=%d must be 0",
                      pdims->reserved);
@@ -434,13 +396,10 @@ int marlnav_rollout_collect(const MarlnavDims *dims, const MarlnavParams *params
     hipStream_t s = (hipStream_t)stream;
     if (int rc = marlnav_observe(dims, params, env->states, env->obstacles, env->target, env->obs,
                                  stream))
-        return fail_step(rc, 0, "marlnav_observe");
+        return fail_step(who, rc, 0, "marlnav_observe");
     hipLaunchKernelGGL(obs_norm_kernel, dim3((unsigned)norm_blocks), dim3(kThreads), 0, s, env->obs,
                        env->norm_mean, env->norm_scale, row_obs, D, rollout->obs);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        return failf(MARLNAV_ELAUNCH, "marlnav_rollout_collect: step 0, normaliser: %s",
-                     hipGetErrorString(e));
+    if (int rc = launch_status()) return fail_step(who, rc, 0, "normaliser");
 
     // ---- the steps (models.py:113-124)
     MarlnavPolicyBuffers pb = *policy;
@@ -455,14 +414,14 @@ int marlnav_rollout_collect(const MarlnavDims *dims, const MarlnavParams *params
         pb.values = rollout->values + t * P;
         if (int rc = marlnav_policy_act(pdims, &pb, policy_seed, policy_step_idx0 + (uint64_t)t,
                                         stream))
-            return fail_step(rc, t, "marlnav_policy_act");
+            return fail_step(who, rc, t, "marlnav_policy_act");
         sb.actions = pb.actions;
         sb.reward = rollout->rewards + t * P;
         sb.terminated = rollout->done + t * P;
         sb.truncated = rollout->truncated + t * P;
         sb.obs_norm = t + 1 < T ? rollout->obs + (t + 1) * row_obs : env->obs_norm;
         if (int rc = marlnav_step(dims, params, &sb, env_step_idx0 + (uint64_t)t, stream))
-            return fail_step(rc, t, "marlnav_step");
+            return fail_step(who, rc, t, "marlnav_step");
         if (sb.states_out) {  // the step wrote the new states there: current from here on
             float *cur = sb.states_out;
             sb.states_out = sb.states;
@@ -473,15 +432,14 @@ int marlnav_rollout_collect(const MarlnavDims *dims, const MarlnavParams *params
     // ---- done = terminated | truncated over the whole stack (models.py:117)
     hipLaunchKernelGGL(merge_flags_kernel, dim3((unsigned)merge_blocks), dim3(kThreads), 0, s,
                        rollout->done, rollout->truncated, nflags, head, nvec);
-    e = hipGetLastError();
-    if (e != hipSuccess)
+    if (launch_status())
         return failf(MARLNAV_ELAUNCH, "marlnav_rollout_collect: after step %lld, flag merge: %s",
-                     (long long)(T - 1), hipGetErrorString(e));
+                     (long long)(T - 1), marlnav_last_error());
     if (want_returns)
         if (int rc = marlnav_discounted_returns(rollout->rewards, rollout->done, T, P, gamma,
                                                 rollout->returns, rollout->returns_stats,
                                                 rollout->returns_work, stream))
-            return fail_step(rc, T - 1, "marlnav_discounted_returns after it");
+            return fail_step(who, rc, T - 1, "marlnav_discounted_returns after it");
     return 0;
 }
 

@@ -136,17 +136,22 @@ def test_buffer_process_gae_sets_both_and_leaves_the_returns(pkg):
 
 
 # ---------------------------------------------------------------- 2. bootstrap
+@pytest.mark.parametrize("offset_floats", [0, 2])
 @pytest.mark.parametrize("H", [5, 50])
 @pytest.mark.parametrize("P,A,O", [(5, 3, 3), (70, 3, 8), (3, 16, 32)])
-def test_values_equal_the_policy_launchs_values(pkg, P, A, O, H):
+def test_values_equal_the_policy_launchs_values(pkg, P, A, O, H, offset_floats):
     policy = tr.make_policy(pkg, A, O, H)
     D = policy.obs_dim
+    n = P * A * D
     g = torch.Generator().manual_seed(P + H)
-    flat = (torch.rand(P * A * D + 1, generator=g) * 2 - 1).to(DEV)
+    flat = (torch.rand(n + 4, generator=g) * 2 - 1).to(DEV)
     zeros = torch.zeros(P * A, 2, device=DEV)
-    # 16-byte aligned rows (the compiled shapes' kernels) and rows 4 bytes off
-    # (the generic kernel)
-    for x in (flat[:-1].clone().view(P, A, D), flat[1:].view(P, A, D)):
+    # rows at offset_floats (0: 16-byte aligned, the compiled shapes' kernels;
+    # 2: 8-byte only, the generic kernel at a compiled shape too) and the same
+    # 4 bytes further on (the generic kernel, scalar loads alone)
+    for off in (offset_floats, offset_floats + 1):
+        x = flat[off:off + n].view(P, A, D)
+        assert x.is_contiguous() and x.data_ptr() % 16 == 4 * off
         policy.step_idx = 7
         want = policy.act(x, eps=zeros)[2]
         got = policy.values(x)
