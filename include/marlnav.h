@@ -535,6 +535,8 @@ typedef struct MarlnavAdamDims {
  * takes the vector path). The slots must not overlap. */
 typedef struct MarlnavAdamBuffers {
     float *param[MARLNAV_ADAM_MAX_TENSORS];       /* updated in place         */
+    /* read only, except by the `_clipped` calls below, which WRITE the
+     * clipped gradient back through these pointers */
     const float *grad[MARLNAV_ADAM_MAX_TENSORS];
     float *exp_avg[MARLNAV_ADAM_MAX_TENSORS];     /* first moment, in place   */
     float *exp_avg_sq[MARLNAV_ADAM_MAX_TENSORS];  /* second moment, in place  */
@@ -644,6 +646,91 @@ int marlnav_ppo_train_phase_mode(int network, const MarlnavPpoDims *dims,
  * negative on bad dims or bounds. */
 int64_t marlnav_ppo_train_work_size(const MarlnavPpoDims *dims, const int64_t *bounds,
                                     int64_t num_batches);
+
+/* Global-norm gradient clipping inside the update: what
+ * torch.nn.utils.clip_grad_norm_(parameters, max_norm) does between
+ * backward() and optimizer.step(), with error_if_nonfinite=False. For one
+ * network's Adam table and max_norm:
+ *   S    = sum over all slots, all elements of (double)g^2   fp64, fixed order
+ *   norm = sqrt(S)
+ *   coef = min(1.0, max_norm / (norm + 1e-6))                fp64; torch's formula
+ *   g'   = (float)((double)g * coef)                         stored back into .grad
+ *   Adam = the element update of marlnav_adam_step from the stored, rounded g'
+ * .grad holds the clipped gradient afterwards: these calls WRITE through
+ * MarlnavAdamBuffers.grad although it is declared const float *. coef == 1.0
+ * (a norm below max_norm - 1e-6, a zero gradient, max_norm = +inf) leaves
+ * every bit of .grad, the parameters, the moments and the count equal to the
+ * unclipped call's. max_norm must be > 0 and not NaN; +inf is allowed and
+ * means "record the norm, clip nothing". A non-finite gradient gives a
+ * non-finite norm and coefficient and poisons the step, as clip_grad_norm_'s
+ * default does; nothing special-cases it.
+ *
+ * Reduction order, fixed, no atomics, equal inputs give equal bits: the
+ * table's elements are cut into items of 4 in table order as for
+ * marlnav_adam_step; a thread forms the fp64 sum of its item's <= 4 squares
+ * in element order; blocks of 256 consecutive items are summed wave by wave
+ * (a fixed shuffle tree, the four waves in order) into one partial per block,
+ * stored to norm_work in block order; the second stage is one block of 256
+ * threads, thread t summing partials t, t + 256, ... in that order, then the
+ * same block sum. The order does not depend on the launch path or on the
+ * slots' alignment.
+ *
+ * Three launches on `stream` after the gradient launches: the square sums;
+ * one block that reduces the partials, publishes coef in the state block
+ * (its last 8 bytes, which marlnav_adam_step never reads), writes *norm_out
+ * and then advances the count; the element update. max_norm travels as a
+ * launch argument: a captured graph keeps the value of capture time.
+ *   norm_work  device, marlnav_grad_norm_work_size(dims) doubles, 8-byte
+ *              aligned, owned by the call while it runs on the stream
+ *   norm_out   device double, 8-byte aligned, or NULL: the norm BEFORE clipping
+ *   norm_log   (train phase) device, num_epochs * num_batches doubles or NULL:
+ *              update k writes [k]
+ * Each call makes every check of its unclipped counterpart
+ * (marlnav_adam_step, marlnav_ppo_actor_update_mode,
+ * marlnav_ppo_critic_update, marlnav_ppo_train_phase_mode) and those of
+ * max_norm, norm_work and norm_out / norm_log before the first launch
+ * (MARLNAV_EINVAL, the message names the field). The clipped phase never
+ * takes the unclipped phase's folded finish launches (those kernels update
+ * elements before the norm exists): an update is the gradient launches of
+ * marlnav_ppo_*_grad and the three above, except for an actor of up to 1024
+ * elements, whose one-block finish launch forms the norm in the same order
+ * and updates behind a block barrier (marlnav_debug_clip_fold below). Either
+ * way it stores what marlnav_ppo_*_update_clipped on the same steps stores,
+ * bit for bit. */
+int64_t marlnav_grad_norm_work_size(const MarlnavAdamDims *dims); /* < 0: bad dims */
+int marlnav_adam_step_clipped(const MarlnavAdamDims *dims, const MarlnavAdamBuffers *bufs,
+                              double max_norm, double *norm_work, double *norm_out,
+                              void *stream);
+int marlnav_ppo_actor_update_clipped(const MarlnavPpoDims *dims, const MarlnavPpoBuffers *bufs,
+                                     double epsilon, double ent_const,
+                                     const MarlnavAdamDims *adam_dims,
+                                     const MarlnavAdamBuffers *adam_bufs, int advantage_mode,
+                                     double max_norm, double *norm_work, double *norm_out,
+                                     void *stream);
+int marlnav_ppo_critic_update_clipped(const MarlnavPpoDims *dims, const MarlnavPpoBuffers *bufs,
+                                      double epsilon, const MarlnavAdamDims *adam_dims,
+                                      const MarlnavAdamBuffers *adam_bufs, double max_norm,
+                                      double *norm_work, double *norm_out, void *stream);
+int marlnav_ppo_train_phase_clipped(int network, const MarlnavPpoDims *dims,
+                                    const MarlnavPpoBuffers *bufs, const int64_t *bounds,
+                                    int64_t num_batches, int64_t num_epochs, double epsilon,
+                                    double ent_const, const MarlnavAdamDims *adam_dims,
+                                    const MarlnavAdamBuffers *adam_bufs, double *loss_log,
+                                    int advantage_mode, double max_norm, double *norm_work,
+                                    double *norm_log, void *stream);
+
+/* Testing and measurement hook (not part of the reference's interface):
+ * whether marlnav_ppo_train_phase_clipped takes the in-block fold for an actor
+ * of up to 1024 elements: actor_finish, one block, re-reads
+ * the gradients it has stored in the reduction order above, forms the norm
+ * and the coefficient in-block and then updates, two launches per update in
+ * place of five, with the same stored bits. Process-wide; 0 or 1 sets it, any
+ * other value only queries; returns the previous setting. The default,
+ * MARLNAV_CLIP_FOLD_DEFAULT, is the measured decision: on (1.1-2.4 us per
+ * update below the five launches at 854 elements, more than the spread of
+ * the repetitions, in both runs of scripts/clip_bench.py). */
+#define MARLNAV_CLIP_FOLD_DEFAULT 1
+int marlnav_debug_clip_fold(int on);
 
 /* The checkpoint rule of MAPPO.get_data (models.py:127-129) on the device: if
  * *mean_rew > *max_rew (fp64; a NaN mean is not greater), copy src[i] to

@@ -182,6 +182,9 @@ EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_for
            "marlnav_gae_work_size", "marlnav_gae_advantages", "marlnav_critic_values",
            "marlnav_ppo_actor_grad_mode", "marlnav_ppo_actor_update_mode",
            "marlnav_ppo_train_phase_mode",
+           "marlnav_grad_norm_work_size", "marlnav_adam_step_clipped",
+           "marlnav_ppo_actor_update_clipped", "marlnav_ppo_critic_update_clipped",
+           "marlnav_ppo_train_phase_clipped", "marlnav_debug_clip_fold",
            "marlnav_last_error", "marlnav_abi_version",
            "marlnav_debug_force_family", "marlnav_debug_last_family",
            "marlnav_debug_acos_range", "marlnav_debug_fastdiv_check")
@@ -277,6 +280,26 @@ def _declare(lib):
                                                  c.c_int64, c.c_double, c.c_double, adam_dims_p,
                                                  adam_bufs_p, _P, c.c_int, _P]
     lib.marlnav_ppo_train_phase_mode.restype = c.c_int
+    # the clipped forms: ..., max_norm, norm_work, norm_out / norm_log, stream
+    lib.marlnav_grad_norm_work_size.argtypes = [adam_dims_p]
+    lib.marlnav_grad_norm_work_size.restype = c.c_int64
+    lib.marlnav_adam_step_clipped.argtypes = [adam_dims_p, adam_bufs_p, c.c_double, _P, _P, _P]
+    lib.marlnav_adam_step_clipped.restype = c.c_int
+    lib.marlnav_ppo_actor_update_clipped.argtypes = [ppo_dims_p, ppo_bufs_p, c.c_double,
+                                                     c.c_double, adam_dims_p, adam_bufs_p,
+                                                     c.c_int, c.c_double, _P, _P, _P]
+    lib.marlnav_ppo_actor_update_clipped.restype = c.c_int
+    lib.marlnav_ppo_critic_update_clipped.argtypes = [ppo_dims_p, ppo_bufs_p, c.c_double,
+                                                      adam_dims_p, adam_bufs_p, c.c_double, _P,
+                                                      _P, _P]
+    lib.marlnav_ppo_critic_update_clipped.restype = c.c_int
+    lib.marlnav_ppo_train_phase_clipped.argtypes = [c.c_int, ppo_dims_p, ppo_bufs_p, i64_p,
+                                                    c.c_int64, c.c_int64, c.c_double, c.c_double,
+                                                    adam_dims_p, adam_bufs_p, _P, c.c_int,
+                                                    c.c_double, _P, _P, _P]
+    lib.marlnav_ppo_train_phase_clipped.restype = c.c_int
+    lib.marlnav_debug_clip_fold.argtypes = [c.c_int]
+    lib.marlnav_debug_clip_fold.restype = c.c_int
     lib.marlnav_last_error.argtypes = []
     lib.marlnav_last_error.restype = c.c_char_p
     lib.marlnav_abi_version.argtypes = []

@@ -28,6 +28,12 @@ reference's weight files, CSVs, params file and figures, and one JSON line.
  instead of the reference's normalised returns.
 
     python -m marlnav_amd --train --gae-lambda 0.95 -np 4096 -bl 16 -bs 8 -ne 4 -nt 1048576
+
+``--max-grad-norm G`` with ``--train`` clips every update's gradient by its
+global L2 norm and adds the two ``_gnorm.csv`` logs; it
+composes with ``--gae-lambda``.
+
+    python -m marlnav_amd --train --max-grad-norm 0.5 -np 4096 -bl 16 -bs 8 -ne 4 -nt 1048576
 """
 import argparse
 import sys
@@ -104,6 +110,9 @@ def build_parser():
     a('--gae-lambda', type=float, default=None, metavar='LAMBDA',
       help='with --train: GAE(lambda) advantages in [0, 1] with own-env pairing, the terminal '
            'reward kept and a bootstrap value (default: the reference\'s normalised returns)')
+    a('--max-grad-norm', type=float, default=None, metavar='G',
+      help='with --train: clip every update\'s gradient to the global L2 norm G > 0, as '
+           'clip_grad_norm_ does (default: no clipping)')
     a('--out-dir', default='.', help='with --train: where weights/, logs/ and plots/ go')
     a('--plot-dir', default='plots', help='directory of the saved figures')
     a('--no-plots', action='store_true', help='skip the figures, print the series')

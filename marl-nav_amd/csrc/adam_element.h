@@ -18,7 +18,7 @@ struct AdamState {
     int64_t step;      // steps taken
     double step_size;  // lr / (1 - beta1^step)
     double bc2_sqrt;   // sqrt(1 - beta2^step)
-    double reserved;
+    double reserved;   // the clipped step's coefficient (below); unused by the unclipped step
 };
 
 struct AdamScalars {
@@ -46,6 +46,24 @@ __device__ __forceinline__ void adam_element(float &p, float g, float &m, float 
     v = (float)__builtin_fma(c.beta2, (double)v, (c.omb2 * gd) * gd);
     const double denom = sqrt((double)v) / c.bc2_sqrt + c.eps;
     p = (float)((double)p - c.step_size * ((double)m / denom));
+}
+
+// ---- global-norm clipping. AdamState.reserved carries the
+// coefficient from the launch that forms the norm to the launch that applies it.
+
+// torch.nn.utils.clip_grad_norm_'s coefficient, its 1e-6 included. A NaN
+// quotient (a non-finite norm) stays NaN: error_if_nonfinite=False poisons
+// the step, as it does there.
+__device__ __forceinline__ double clip_coef(double norm, double max_norm)
+{
+    const double q = max_norm / (norm + 1e-6);
+    return q > 1.0 ? 1.0 : q;
+}
+
+// the gradient as stored back into .grad: coef == 1.0 returns g's own bits
+__device__ __forceinline__ float clipped_grad(float g, double coef)
+{
+    return (float)((double)g * coef);
 }
 
 }  // namespace marlnav_adam

@@ -32,6 +32,23 @@
 // rule as a copy launch and one bookkeeping thread. The `_mode` forms of the
 // actor's calls carry the pairing of advantages to agent rows;
 // the forms without it are calls of them with MARLNAV_ADVANTAGE_REFERENCE.
+//
+// The `_clipped` forms clip the gradient by its global L2 norm
+// between the gradient launches and the update: three launches in place of
+// the two. grad_sqsum writes one fp64 partial per block of adam_apply's items;
+// adam_advance_clip (one block) reduces them, publishes the coefficient in
+// AdamState.reserved, writes the norm and advances the count last;
+// adam_apply<true> scales each gradient, stores it back and updates from the
+// stored value. Datum by datum: .grad is written by the gradient launches
+// and by adam_apply<true>, read by grad_sqsum and adam_apply<true> (each
+// element by the one thread that rewrites it); the partials are written by
+// grad_sqsum and read by adam_advance_clip; the state block is written by
+// adam_advance_clip alone and read by adam_apply<true>. Stream order puts
+// every read after its write, and no launch reads what another thread of it
+// writes except through block_sum's barrier. The clipped phase does not use
+// the unclipped phase's folded finish kernels; for an actor of up to 1024
+// elements it takes marlnav_ppo.hip's in-block variant of actor_finish, which
+// stores the same bits in two launches (marlnav_debug_clip_fold turns it off).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -49,12 +66,17 @@ namespace {
 #include "host_util.h"
 
 constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
 constexpr int kSlots = MARLNAV_ADAM_MAX_TENSORS;
 constexpr int64_t kMaxElements = (int64_t)1 << 40;  // all slots together
 
 using marlnav_adam::AdamScalars;
 using marlnav_adam::AdamState;
 using marlnav_adam::adam_element;
+using marlnav_adam::clip_coef;
+using marlnav_adam::clipped_grad;
+
+#include "block_sum.h"
 
 struct AdamArgs {
     float *param[kSlots];
@@ -76,6 +98,11 @@ __global__ void __launch_bounds__(64) adam_advance(AdamState *s, double lr, doub
     marlnav_adam::adam_advance_one(s, lr, beta1, beta2);
 }
 
+// kClip (the clipped step): each gradient is scaled by the
+// coefficient that adam_advance_clip published, stored back into .grad, and
+// the element is updated from that stored value. The unclipped instantiation
+// is the kernel of marlnav_adam_step.
+template <bool kClip>
 __global__ void __launch_bounds__(kThreads) adam_apply(AdamArgs a)
 {
     const int64_t item = (int64_t)blockIdx.x * kThreads + threadIdx.x;
@@ -108,13 +135,22 @@ __global__ void __launch_bounds__(kThreads) adam_apply(AdamArgs a)
     c.bc2_sqrt = a.state->bc2_sqrt;
     c.maximize = a.maximize != 0;
 
+    double coef = 1.0;  // kClip only
+    if constexpr (kClip) coef = a.state->reserved;
     const int64_t e0 = (item - first) * 4;  // < n: a slot has ceil(n / 4) items
     const int64_t left = n - e0;
     if (vec && left >= 4) {
         float4 p4 = *reinterpret_cast<const float4 *>(p + e0);
-        const float4 g4 = *reinterpret_cast<const float4 *>(g + e0);
+        float4 g4 = *reinterpret_cast<const float4 *>(g + e0);
         float4 m4 = *reinterpret_cast<const float4 *>(m + e0);
         float4 v4 = *reinterpret_cast<const float4 *>(v + e0);
+        if constexpr (kClip) {
+            g4.x = clipped_grad(g4.x, coef);
+            g4.y = clipped_grad(g4.y, coef);
+            g4.z = clipped_grad(g4.z, coef);
+            g4.w = clipped_grad(g4.w, coef);
+            *reinterpret_cast<float4 *>(const_cast<float *>(g) + e0) = g4;
+        }
         adam_element(p4.x, g4.x, m4.x, v4.x, c);
         adam_element(p4.y, g4.y, m4.y, v4.y, c);
         adam_element(p4.z, g4.z, m4.z, v4.z, c);
@@ -126,7 +162,12 @@ __global__ void __launch_bounds__(kThreads) adam_apply(AdamArgs a)
         const int cnt = left < 4 ? (int)left : 4;
         for (int j = 0; j < cnt; ++j) {
             float pj = p[e0 + j], mj = m[e0 + j], vj = v[e0 + j];
-            adam_element(pj, g[e0 + j], mj, vj, c);
+            float gj = g[e0 + j];
+            if constexpr (kClip) {
+                gj = clipped_grad(gj, coef);
+                const_cast<float *>(g)[e0 + j] = gj;
+            }
+            adam_element(pj, gj, mj, vj, c);
             m[e0 + j] = mj;
             v[e0 + j] = vj;
             p[e0 + j] = pj;
@@ -134,10 +175,75 @@ __global__ void __launch_bounds__(kThreads) adam_apply(AdamArgs a)
     }
 }
 
+// The square sum of every gradient of the table, first stage:
+// thread = item as adam_apply; a thread's fp64 sum of its <= 4 squares in
+// element order (0 past the table's last item), then block_sum; block b's
+// partial goes to partials[b]. Reads .grad only.
+__global__ void __launch_bounds__(kThreads) grad_sqsum(AdamArgs a, double *partials)
+{
+    __shared__ double sh[kWaves];
+    const int64_t item = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    double acc = 0.0;
+    if (item < a.item_end[kSlots - 1]) {
+        const float *g = a.grad[0];
+        int64_t n = a.numel[0], first = 0;
+        bool vec = a.vec_mask & 1u;
+#pragma unroll
+        for (int i = 1; i < kSlots; ++i)
+            if (item >= a.item_end[i - 1]) {  // never true for an unused slot
+                g = a.grad[i];
+                n = a.numel[i];
+                first = a.item_end[i - 1];
+                vec = (a.vec_mask >> i) & 1u;
+            }
+        const int64_t e0 = (item - first) * 4;
+        const int64_t left = n - e0;
+        if (vec && left >= 4) {
+            const float4 g4 = *reinterpret_cast<const float4 *>(g + e0);
+            acc = (double)g4.x * (double)g4.x;
+            acc += (double)g4.y * (double)g4.y;
+            acc += (double)g4.z * (double)g4.z;
+            acc += (double)g4.w * (double)g4.w;
+        } else {
+            const int cnt = left < 4 ? (int)left : 4;
+            for (int j = 0; j < cnt; ++j) {
+                const double gj = (double)g[e0 + j];
+                acc += gj * gj;
+            }
+        }
+    }
+    const double t = block_sum(acc, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = t;
+}
+
+// Second stage and the count's advance, one block, in place of adam_advance:
+// thread t sums partials[t], [t + 256], ... in that order, block_sum adds the
+// 256 sums; thread 0 then publishes the coefficient in the state block,
+// writes the norm and, last, advances the count (no other thread writes, and
+// nothing written here is read in this launch except through block_sum's
+// barrier).
+__global__ void __launch_bounds__(kThreads) adam_advance_clip(AdamState *s, double lr,
+                                                              double beta1, double beta2,
+                                                              const double *partials,
+                                                              int64_t num_partials,
+                                                              double max_norm, double *norm_out)
+{
+    __shared__ double sh[kWaves];
+    if (blockIdx.x != 0) return;
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < num_partials; i += kThreads) acc += partials[i];
+    const double total = block_sum(acc, sh);
+    if (threadIdx.x != 0) return;
+    const double norm = sqrt(total);
+    s->reserved = clip_coef(norm, max_norm);
+    if (norm_out) *norm_out = norm;
+    marlnav_adam::adam_advance_one(s, lr, beta1, beta2);
+}
+
 // ---- host side
 inline uintptr_t addr(const void *p) { return reinterpret_cast<uintptr_t>(p); }
 
-int check_adam(const MarlnavAdamDims *d, const MarlnavAdamBuffers *b)
+int check_adam_dims(const MarlnavAdamDims *d)
 {
     if (!d) return marlnav_internal_fail(MARLNAV_EINVAL, "adam dims is NULL");
     if (d->num_tensors < 1 || d->num_tensors > kSlots)
@@ -162,6 +268,13 @@ int check_adam(const MarlnavAdamDims *d, const MarlnavAdamBuffers *b)
         return failf(MARLNAV_EINVAL, "adam: eps=%g must be finite and >= 0", d->eps);
     if (d->reserved != 0)
         return failf(MARLNAV_EINVAL, "adam: reserved=%lld must be 0", (long long)d->reserved);
+    return 0;
+}
+
+int check_adam(const MarlnavAdamDims *d, const MarlnavAdamBuffers *b)
+{
+    const int rc = check_adam_dims(d);
+    if (rc) return rc;
     if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "adam buffers is NULL");
     for (int i = 0; i < d->num_tensors; ++i) {
         const void *ptr[4] = {b->param[i], b->grad[i], b->exp_avg[i], b->exp_avg_sq[i]};
@@ -178,8 +291,38 @@ int check_adam(const MarlnavAdamDims *d, const MarlnavAdamBuffers *b)
     return 0;
 }
 
-// checked arguments only
-int enqueue_adam(const MarlnavAdamDims *d, const MarlnavAdamBuffers *b, hipStream_t s)
+// blocks of adam_apply / grad_sqsum over the table: ceil(items / 256)
+int64_t table_blocks(const MarlnavAdamDims *d)
+{
+    int64_t items = 0;
+    for (int i = 0; i < d->num_tensors; ++i) items += (d->numel[i] + 3) / 4;
+    return (items + kThreads - 1) / kThreads;
+}
+
+// the clipped step's own arguments; norm_out is the call's norm_out / norm_log
+struct ClipArgs {
+    double max_norm;
+    double *norm_work;
+    double *norm_out;  // of the next step; NULL: not recorded
+};
+
+int check_clip(double max_norm, const void *norm_work, const void *norm_out, const char *out_name)
+{
+    if (!(max_norm > 0.0))  // a NaN is not greater
+        return failf(MARLNAV_EINVAL, "clip: max_norm=%g must be > 0 (+inf: record the norm only)",
+                     max_norm);
+    if (!norm_work) return marlnav_internal_fail(MARLNAV_EINVAL, "clip: norm_work is NULL");
+    if (addr(norm_work) & 7u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "clip: norm_work must be 8-byte aligned");
+    if (addr(norm_out) & 7u)
+        return failf(MARLNAV_EINVAL, "clip: %s must be 8-byte aligned", out_name);
+    return 0;
+}
+
+// checked arguments only. clip NULL: the two launches of marlnav_adam_step;
+// given: the three of marlnav_adam_step_clipped.
+int enqueue_adam(const MarlnavAdamDims *d, const MarlnavAdamBuffers *b, hipStream_t s,
+                 const ClipArgs *clip = nullptr)
 {
     AdamArgs a;
     int64_t items = 0;
@@ -207,10 +350,18 @@ int enqueue_adam(const MarlnavAdamDims *d, const MarlnavAdamBuffers *b, hipStrea
     a.omb2 = 1.0 - d->beta2;
     a.eps = d->eps;
     a.maximize = d->maximize;
-    hipLaunchKernelGGL(adam_advance, dim3(1), dim3(64), 0, s, state, d->lr, d->beta1, d->beta2);
     // items <= 2^38 + 8: the grid fits 31 bits
-    hipLaunchKernelGGL(adam_apply, dim3((unsigned)((items + kThreads - 1) / kThreads)),
-                       dim3(kThreads), 0, s, a);
+    const dim3 grid((unsigned)((items + kThreads - 1) / kThreads));
+    if (clip) {
+        hipLaunchKernelGGL(grad_sqsum, grid, dim3(kThreads), 0, s, a, clip->norm_work);
+        hipLaunchKernelGGL(adam_advance_clip, dim3(1), dim3(kThreads), 0, s, state, d->lr,
+                           d->beta1, d->beta2, clip->norm_work, (int64_t)grid.x, clip->max_norm,
+                           clip->norm_out);
+        hipLaunchKernelGGL(adam_apply<true>, grid, dim3(kThreads), 0, s, a);
+        return launch_status();
+    }
+    hipLaunchKernelGGL(adam_advance, dim3(1), dim3(64), 0, s, state, d->lr, d->beta1, d->beta2);
+    hipLaunchKernelGGL(adam_apply<false>, grid, dim3(kThreads), 0, s, a);
     return launch_status();
 }
 
@@ -249,11 +400,31 @@ extern "C" int marlnav_adam_step(const MarlnavAdamDims *d, const MarlnavAdamBuff
     return enqueue_adam(d, b, (hipStream_t)stream);
 }
 
-extern "C" int marlnav_ppo_actor_update_mode(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
-                                             double epsilon, double ent_const,
-                                             const MarlnavAdamDims *ad,
-                                             const MarlnavAdamBuffers *ab, int advantage_mode,
-                                             void *stream)
+extern "C" int64_t marlnav_grad_norm_work_size(const MarlnavAdamDims *d)
+{
+    const int rc = check_adam_dims(d);
+    if (rc) return rc;
+    return table_blocks(d);
+}
+
+extern "C" int marlnav_adam_step_clipped(const MarlnavAdamDims *d, const MarlnavAdamBuffers *b,
+                                         double max_norm, double *norm_work, double *norm_out,
+                                         void *stream)
+{
+    int rc = check_adam(d, b);
+    if (rc) return rc;
+    rc = check_clip(max_norm, norm_work, norm_out, "norm_out");
+    if (rc) return rc;
+    const ClipArgs clip = {max_norm, norm_work, norm_out};
+    return enqueue_adam(d, b, (hipStream_t)stream, &clip);
+}
+
+namespace {
+
+// clip NULL: marlnav_ppo_actor_update_mode; given: its _clipped form
+int actor_update(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
+                 double ent_const, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
+                 int advantage_mode, const ClipArgs *clip, void *stream)
 {
     // every check of both halves before the first launch: the ppo dims
     // (marlnav_ppo_work_size runs them), the Adam arguments, the table; the
@@ -272,9 +443,56 @@ extern "C" int marlnav_ppo_actor_update_mode(const MarlnavPpoDims *d, const Marl
                                  "actor_mu_b",  "actor_std_w", "actor_std_b"};
     rc = check_table("actor", 6, w, gw, size, name, ad, ab);
     if (rc) return rc;
+    if (clip) rc = check_clip(clip->max_norm, clip->norm_work, clip->norm_out, "norm_out");
+    if (rc) return rc;
     rc = marlnav_ppo_actor_grad_mode(d, b, epsilon, ent_const, advantage_mode, stream);
     if (rc) return rc;
-    return enqueue_adam(ad, ab, (hipStream_t)stream);
+    return enqueue_adam(ad, ab, (hipStream_t)stream, clip);
+}
+
+int critic_update(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
+                  const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, const ClipArgs *clip,
+                  void *stream)
+{
+    if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
+    if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
+    int rc = check_adam(ad, ab);
+    if (rc) return rc;
+    const int64_t H = d->hidden_size, AD = (int64_t)d->num_agents * d->obs_dim;
+    const float *const w[4] = {b->critic_fc1_w, b->critic_fc1_b, b->critic_fc2_w, b->critic_fc2_b};
+    float *const gw[4] = {b->grad_critic_fc1_w, b->grad_critic_fc1_b, b->grad_critic_fc2_w,
+                          b->grad_critic_fc2_b};
+    const int64_t size[4] = {H * AD, H, H, 1};
+    const char *const name[4] = {"critic_fc1_w", "critic_fc1_b", "critic_fc2_w", "critic_fc2_b"};
+    rc = check_table("critic", 4, w, gw, size, name, ad, ab);
+    if (rc) return rc;
+    if (clip) rc = check_clip(clip->max_norm, clip->norm_work, clip->norm_out, "norm_out");
+    if (rc) return rc;
+    rc = marlnav_ppo_critic_grad(d, b, epsilon, stream);
+    if (rc) return rc;
+    return enqueue_adam(ad, ab, (hipStream_t)stream, clip);
+}
+
+}  // namespace
+
+extern "C" int marlnav_ppo_actor_update_mode(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                                             double epsilon, double ent_const,
+                                             const MarlnavAdamDims *ad,
+                                             const MarlnavAdamBuffers *ab, int advantage_mode,
+                                             void *stream)
+{
+    return actor_update(d, b, epsilon, ent_const, ad, ab, advantage_mode, nullptr, stream);
+}
+
+extern "C" int marlnav_ppo_actor_update_clipped(const MarlnavPpoDims *d,
+                                                const MarlnavPpoBuffers *b, double epsilon,
+                                                double ent_const, const MarlnavAdamDims *ad,
+                                                const MarlnavAdamBuffers *ab, int advantage_mode,
+                                                double max_norm, double *norm_work,
+                                                double *norm_out, void *stream)
+{
+    const ClipArgs clip = {max_norm, norm_work, norm_out};
+    return actor_update(d, b, epsilon, ent_const, ad, ab, advantage_mode, &clip, stream);
 }
 
 extern "C" int marlnav_ppo_actor_update(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
@@ -290,21 +508,18 @@ extern "C" int marlnav_ppo_critic_update(const MarlnavPpoDims *d, const MarlnavP
                                          double epsilon, const MarlnavAdamDims *ad,
                                          const MarlnavAdamBuffers *ab, void *stream)
 {
-    if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
-    if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
-    int rc = check_adam(ad, ab);
-    if (rc) return rc;
-    const int64_t H = d->hidden_size, AD = (int64_t)d->num_agents * d->obs_dim;
-    const float *const w[4] = {b->critic_fc1_w, b->critic_fc1_b, b->critic_fc2_w, b->critic_fc2_b};
-    float *const gw[4] = {b->grad_critic_fc1_w, b->grad_critic_fc1_b, b->grad_critic_fc2_w,
-                          b->grad_critic_fc2_b};
-    const int64_t size[4] = {H * AD, H, H, 1};
-    const char *const name[4] = {"critic_fc1_w", "critic_fc1_b", "critic_fc2_w", "critic_fc2_b"};
-    rc = check_table("critic", 4, w, gw, size, name, ad, ab);
-    if (rc) return rc;
-    rc = marlnav_ppo_critic_grad(d, b, epsilon, stream);
-    if (rc) return rc;
-    return enqueue_adam(ad, ab, (hipStream_t)stream);
+    return critic_update(d, b, epsilon, ad, ab, nullptr, stream);
+}
+
+extern "C" int marlnav_ppo_critic_update_clipped(const MarlnavPpoDims *d,
+                                                 const MarlnavPpoBuffers *b, double epsilon,
+                                                 const MarlnavAdamDims *ad,
+                                                 const MarlnavAdamBuffers *ab, double max_norm,
+                                                 double *norm_work, double *norm_out,
+                                                 void *stream)
+{
+    const ClipArgs clip = {max_norm, norm_work, norm_out};
+    return critic_update(d, b, epsilon, ad, ab, &clip, stream);
 }
 
 // =========================================================================
@@ -314,8 +529,17 @@ __attribute__((visibility("hidden"))) int marlnav_internal_ppo_fold(
     int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
     double ent_const, int advantage_mode, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
     void *stream, int check_only);
+__attribute__((visibility("hidden"))) int marlnav_internal_ppo_actor_clip_fold(
+    const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon, double ent_const,
+    int advantage_mode, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, double max_norm,
+    double *norm_out, void *stream);
 
 namespace {
+
+// whether the clipped phase folds the actor's clip and Adam step into
+// actor_finish (marlnav_debug_clip_fold; the default is the measured decision
+// of DESIGN.md §16)
+int g_clip_fold = MARLNAV_CLIP_FOLD_DEFAULT;
 
 // the (lo, hi) list against the buffer's steps
 int check_bounds(const MarlnavPpoDims *d, const int64_t *bounds, int64_t num_batches)
@@ -369,13 +593,14 @@ extern "C" int64_t marlnav_ppo_train_work_size(const MarlnavPpoDims *d, const in
     return need;
 }
 
-extern "C" int marlnav_ppo_train_phase_mode(int network, const MarlnavPpoDims *d,
-                                            const MarlnavPpoBuffers *b, const int64_t *bounds,
-                                            int64_t num_batches, int64_t num_epochs,
-                                            double epsilon, double ent_const,
-                                            const MarlnavAdamDims *ad,
-                                            const MarlnavAdamBuffers *ab, double *loss_log,
-                                            int advantage_mode, void *stream)
+namespace {
+
+// clip NULL: marlnav_ppo_train_phase_mode; given: its _clipped form, whose
+// norm_out is the norm_log (update k writes [k]) or NULL
+int train_phase(int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                const int64_t *bounds, int64_t num_batches, int64_t num_epochs, double epsilon,
+                double ent_const, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
+                double *loss_log, int advantage_mode, const ClipArgs *clip, void *stream)
 {
     // ---- every check before the first launch
     if (network != MARLNAV_NETWORK_ACTOR && network != MARLNAV_NETWORK_CRITIC)
@@ -417,6 +642,8 @@ extern "C" int marlnav_ppo_train_phase_mode(int network, const MarlnavPpoDims *d
         rc = check_table("critic", 4, w, gw, size, name, ad, ab);
     }
     if (rc) return rc;
+    if (clip) rc = check_clip(clip->max_norm, clip->norm_work, clip->norm_out, "norm_log");
+    if (rc) return rc;
     if (!b->obs) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer obs is NULL");
     if (need_values && !b->values)
         return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer values is NULL");
@@ -436,12 +663,63 @@ extern "C" int marlnav_ppo_train_phase_mode(int network, const MarlnavPpoDims *d
     for (int64_t e = 0; e < num_epochs; ++e)
         for (int64_t j = 0; j < num_batches; ++j, ++k) {
             minibatch(d, b, bounds[2 * j], bounds[2 * j + 1], loss_log + k, &md, &mb);
+            if (clip) {
+                double *const norm_k = clip->norm_out ? clip->norm_out + k : nullptr;
+                if (network == MARLNAV_NETWORK_ACTOR && g_clip_fold) {
+                    // a small actor: norm, clip and update inside actor_finish
+                    rc = marlnav_internal_ppo_actor_clip_fold(&md, &mb, epsilon, ent_const,
+                                                              advantage_mode, ad, ab,
+                                                              clip->max_norm, norm_k, stream);
+                    if (rc < 0) return rc;
+                    if (rc == 0) continue;
+                }
+                // the folded finish kernels of the unclipped phase update
+                // elements before the norm exists: the gradient launches alone,
+                // then the clipped step
+                rc = network == MARLNAV_NETWORK_ACTOR
+                         ? marlnav_ppo_actor_grad_mode(&md, &mb, epsilon, ent_const,
+                                                       advantage_mode, stream)
+                         : marlnav_ppo_critic_grad(&md, &mb, epsilon, stream);
+                if (rc) return rc;
+                const ClipArgs ck = {clip->max_norm, clip->norm_work, norm_k};
+                rc = enqueue_adam(ad, ab, (hipStream_t)stream, &ck);
+                if (rc) return rc;
+                continue;
+            }
             rc = marlnav_internal_ppo_fold(network, &md, &mb, epsilon, ent_const, advantage_mode,
                                            ad, ab, stream, 0);
             if (rc == 1) rc = enqueue_adam(ad, ab, (hipStream_t)stream);  // not folded
             if (rc) return rc;
         }
     return 0;
+}
+
+}  // namespace
+
+extern "C" int marlnav_ppo_train_phase_mode(int network, const MarlnavPpoDims *d,
+                                            const MarlnavPpoBuffers *b, const int64_t *bounds,
+                                            int64_t num_batches, int64_t num_epochs,
+                                            double epsilon, double ent_const,
+                                            const MarlnavAdamDims *ad,
+                                            const MarlnavAdamBuffers *ab, double *loss_log,
+                                            int advantage_mode, void *stream)
+{
+    return train_phase(network, d, b, bounds, num_batches, num_epochs, epsilon, ent_const, ad, ab,
+                       loss_log, advantage_mode, nullptr, stream);
+}
+
+extern "C" int marlnav_ppo_train_phase_clipped(int network, const MarlnavPpoDims *d,
+                                               const MarlnavPpoBuffers *b, const int64_t *bounds,
+                                               int64_t num_batches, int64_t num_epochs,
+                                               double epsilon, double ent_const,
+                                               const MarlnavAdamDims *ad,
+                                               const MarlnavAdamBuffers *ab, double *loss_log,
+                                               int advantage_mode, double max_norm,
+                                               double *norm_work, double *norm_log, void *stream)
+{
+    const ClipArgs clip = {max_norm, norm_work, norm_log};
+    return train_phase(network, d, b, bounds, num_batches, num_epochs, epsilon, ent_const, ad, ab,
+                       loss_log, advantage_mode, &clip, stream);
 }
 
 extern "C" int marlnav_ppo_train_phase(int network, const MarlnavPpoDims *d,
@@ -454,6 +732,13 @@ extern "C" int marlnav_ppo_train_phase(int network, const MarlnavPpoDims *d,
     return marlnav_ppo_train_phase_mode(network, d, b, bounds, num_batches, num_epochs, epsilon,
                                         ent_const, ad, ab, loss_log, MARLNAV_ADVANTAGE_REFERENCE,
                                         stream);
+}
+
+extern "C" int marlnav_debug_clip_fold(int on)
+{
+    const int before = g_clip_fold;
+    if (on == 0 || on == 1) g_clip_fold = on;
+    return before;
 }
 
 // =========================================================================

@@ -139,6 +139,24 @@ __device__ __forceinline__ void fold_element(const FoldArgs &f, int slot, int64_
     f.param[slot][e] = p;
 }
 
+// The clipped update folded into actor_finish: FoldArgs plus
+// the clip's own arguments. actor_pass takes the same AdvArgs as for FoldArgs.
+struct ClipFoldArgs {
+    FoldArgs f;
+    double max_norm;
+    double *norm_out;  // the norm before clipping, or NULL
+};
+
+// element e of one slot with the clip: the gradient scaled, stored back into
+// .grad and the element updated from the stored value (adam_apply<true>)
+__device__ __forceinline__ void clip_fold_element(const FoldArgs &f, int slot, int64_t e,
+                                                  float *grad, double coef, const AdamScalars &c)
+{
+    const float gc = marlnav_adam::clipped_grad(grad[e], coef);
+    grad[e] = gc;
+    fold_element(f, slot, e, gc, c);
+}
+
 // The kernels below take the fold's arguments as a trailing pack: empty for
 // the launches of marlnav_ppo_*_grad / _update, whose instantiations are the
 // kernels as they were; one AdvArgs / FoldArgs for the folded ones.
@@ -147,6 +165,17 @@ __device__ __forceinline__ const T &only(const T &x)
 {
     return x;
 }
+
+template <class... X>
+struct is_clip_fold {
+    static constexpr bool value = false;
+};
+template <>
+struct is_clip_fold<ClipFoldArgs> {
+    static constexpr bool value = true;
+};
+// 16 blocks of 256 items: far above what the 1024-element fold limit needs (2)
+constexpr int kClipFoldMaxBlocks = 16;
 
 // p[0] + p[stride] + ... (n terms) in that order, the loads of eight terms
 // issued before their adds (a rolled loop pays one memory round trip per term)
@@ -451,7 +480,73 @@ __global__ void __launch_bounds__(kThreads) actor_finish(PpoArgs g, X... x)
         else
             g.b.grad_actor_fc1_b[j] = (float)a;
     }
-    if constexpr (sizeof...(X) != 0) {
+    if constexpr (sizeof...(X) != 0 && is_clip_fold<X...>::value) {
+        // CLIP: every gradient is stored; behind the barrier the block re-reads
+        // .grad in the canonical order of marlnav_adam.hip's grad_sqsum /
+        // adam_advance_clip (items of 4 in table order, block_sum per 256
+        // items, the partials summed by thread t = t, t + 256, ..., block_sum),
+        // forms the coefficient, and updates from the scaled, stored gradient.
+        // The totals in s_fin are dead by now: its head is the scratch.
+        __syncthreads();
+        const ClipFoldArgs &cf = only(x...);
+        const FoldArgs &f = cf.f;
+        float *const gp[6] = {g.b.grad_actor_fc1_w, g.b.grad_actor_fc1_b, g.b.grad_actor_mu_w,
+                              g.b.grad_actor_mu_b,  g.b.grad_actor_std_w, g.b.grad_actor_std_b};
+        const int n[6] = {H * D, H, 2 * H, 2, 2 * H, 2};
+        int end[6], items = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            items += (n[i] + 3) / 4;
+            end[i] = items;
+        }
+        double *sh = s_fin;                  // kWaves
+        double *s_part = s_fin + kWaves;     // <= kClipFoldMaxBlocks partials
+        double *s_coef = s_part + kClipFoldMaxBlocks;
+        const int nb = (items + kThreads - 1) / kThreads;
+        for (int blk = 0; blk < nb; ++blk) {
+            const int item = blk * kThreads + t;
+            double acc = 0.0;
+            if (item < items) {
+                int slot = 0;
+#pragma unroll
+                for (int i = 1; i < 6; ++i)
+                    if (item >= end[i - 1]) slot = i;
+                const int e0 = (item - (slot ? end[slot - 1] : 0)) * 4;
+                const int left = n[slot] - e0;
+                const int cnt = left < 4 ? left : 4;
+                for (int j = 0; j < cnt; ++j) {
+                    const double gj = (double)gp[slot][e0 + j];
+                    acc += gj * gj;
+                }
+            }
+            const double part = block_sum(acc, sh);
+            if (t == 0) s_part[blk] = part;
+        }
+        __syncthreads();
+        const double total = block_sum(t < nb ? 0.0 + s_part[t] : 0.0, sh);
+        if (t == 0) {
+            const double norm = sqrt(total);
+            const double coef = marlnav_adam::clip_coef(norm, cf.max_norm);
+            *s_coef = coef;
+            const_cast<AdamState *>(f.state)->reserved = coef;  // as adam_advance_clip leaves it
+            if (cf.norm_out) *cf.norm_out = norm;
+        }
+        __syncthreads();
+        const double coef = *s_coef;
+        const AdamScalars c = fold_scalars(f);
+        for (int idx = t; idx < 4 * H; idx += kThreads) {
+            const int r = idx / H, j = idx - r * H;
+            clip_fold_element(f, r < 2 ? 2 : 4, (r & 1) * H + j, gp[r < 2 ? 2 : 4], coef, c);
+        }
+        if (t < 4) clip_fold_element(f, t < 2 ? 3 : 5, t & 1, gp[t < 2 ? 3 : 5], coef, c);
+        for (int64_t idx = t; idx < (int64_t)H * ncol; idx += kThreads) {
+            const int j = (int)(idx / ncol), cc = (int)(idx - (int64_t)j * ncol);
+            if (cc < D)
+                clip_fold_element(f, 0, (int64_t)j * D + cc, gp[0], coef, c);
+            else
+                clip_fold_element(f, 1, j, gp[1], coef, c);
+        }
+    } else if constexpr (sizeof...(X) != 0) {
         __syncthreads();
         const FoldArgs &f = only(x...);
         const AdamScalars c = fold_scalars(f);
@@ -973,7 +1068,7 @@ int check_critic_bufs(const MarlnavPpoBuffers *b)
 // marlnav_ppo_actor_grad; given: the same two with the Adam step folded in.
 int enqueue_actor(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
                   double ent_const, int advantage_mode, const AdvArgs *adv, const FoldArgs *fold,
-                  hipStream_t s)
+                  hipStream_t s, const ClipFoldArgs *clip = nullptr)
 {
     PpoArgs a = make_args(d, b);
     actor_grid(a.M, a.rows_per_block, a.nblocks);
@@ -988,7 +1083,13 @@ int enqueue_actor(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double ep
     const dim3 grid((unsigned)a.nblocks), blk(kThreads);
     const size_t lds = actor_lds_bytes(a.D);
     const bool env = advantage_mode == MARLNAV_ADVANTAGE_ENV;
-    if (fold) {
+    if (clip) {  // the clipped update folded in (fold is NULL)
+        if (env)
+            hipLaunchKernelGGL((actor_pass<kPairEnv>), grid, blk, lds, s, a, *adv);
+        else
+            hipLaunchKernelGGL((actor_pass<kPairReference>), grid, blk, lds, s, a, *adv);
+        hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), fin_lds, s, a, *clip);
+    } else if (fold) {
         if (env)
             hipLaunchKernelGGL((actor_pass<kPairEnv>), grid, blk, lds, s, a, *adv);
         else
@@ -1110,6 +1211,52 @@ extern "C" int marlnav_ppo_critic_grad(const MarlnavPpoDims *d, const MarlnavPpo
 constexpr int64_t kActorFoldMaxElements = 1024;
 constexpr int64_t kCriticFoldMaxRows = (int64_t)1 << 17;
 
+namespace {
+
+void fold_args(const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, AdvArgs *adv, FoldArgs *f)
+{
+    adv->state = static_cast<AdamState *>(ab->state);
+    adv->lr = ad->lr;
+    adv->beta1 = ad->beta1;
+    adv->beta2 = ad->beta2;
+    for (int i = 0; i < 6; ++i) {
+        const bool used = i < ad->num_tensors;
+        f->param[i] = used ? ab->param[i] : nullptr;
+        f->exp_avg[i] = used ? ab->exp_avg[i] : nullptr;
+        f->exp_avg_sq[i] = used ? ab->exp_avg_sq[i] : nullptr;
+    }
+    f->state = adv->state;
+    f->beta1 = ad->beta1;
+    f->beta2 = ad->beta2;
+    f->omb1 = 1.0 - ad->beta1;
+    f->omb2 = 1.0 - ad->beta2;
+    f->eps = ad->eps;
+    f->maximize = ad->maximize;
+}
+
+}  // namespace
+
+// One clipped actor update for marlnav_ppo_train_phase_clipped with the clip
+// and the Adam step inside actor_finish (two launches), where the actor is
+// within the fold limit: returns 0 with both launches enqueued, 1 with nothing
+// enqueued (a larger actor: the caller enqueues the unfolded update), negative
+// on an error. Checked arguments only, as marlnav_internal_ppo_fold.
+__attribute__((visibility("hidden"))) int marlnav_internal_ppo_actor_clip_fold(
+    const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon, double ent_const,
+    int advantage_mode, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, double max_norm,
+    double *norm_out, void *stream)
+{
+    const int64_t H = d->hidden_size, D = d->obs_dim;
+    if (H * (D + 1) + 4 * H + 4 > kActorFoldMaxElements) return 1;
+    AdvArgs adv;
+    ClipFoldArgs c;
+    fold_args(ad, ab, &adv, &c.f);
+    c.max_norm = max_norm;
+    c.norm_out = norm_out;
+    return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, &adv, nullptr,
+                         (hipStream_t)stream, &c);
+}
+
 // One minibatch update for marlnav_ppo_train_phase (marlnav_adam.hip), which
 // has checked the Adam arguments and that the table is this network's own.
 // network 0: the actor, 1: the critic (advantage_mode, checked by the caller,
@@ -1138,24 +1285,8 @@ __attribute__((visibility("hidden"))) int marlnav_internal_ppo_fold(
         return rc ? rc : 1;
     }
     AdvArgs adv;
-    adv.state = static_cast<AdamState *>(ab->state);
-    adv.lr = ad->lr;
-    adv.beta1 = ad->beta1;
-    adv.beta2 = ad->beta2;
     FoldArgs f;
-    for (int i = 0; i < 6; ++i) {
-        const bool used = i < ad->num_tensors;
-        f.param[i] = used ? ab->param[i] : nullptr;
-        f.exp_avg[i] = used ? ab->exp_avg[i] : nullptr;
-        f.exp_avg_sq[i] = used ? ab->exp_avg_sq[i] : nullptr;
-    }
-    f.state = adv.state;
-    f.beta1 = ad->beta1;
-    f.beta2 = ad->beta2;
-    f.omb1 = 1.0 - ad->beta1;
-    f.omb2 = 1.0 - ad->beta2;
-    f.eps = ad->eps;
-    f.maximize = ad->maximize;
+    fold_args(ad, ab, &adv, &f);
     if (network == 0)
         return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, &adv, &f,
                              (hipStream_t)stream);

@@ -697,29 +697,52 @@ class FusedPPO(object):
         order."""
         return [t for f, t in self._params if f.startswith(which)]
 
-    def actor_update(self, buffer, lo, hi, adam):
+    def actor_update(self, buffer, lo, hi, adam, max_grad_norm=None, norm_out=None):
         """``actor_loss_grad(buffer, lo, hi)`` then ``adam.step()`` as ONE C
         call (``marlnav_ppo_actor_update``): four launches on the current
         stream with no host work between them, bit-identical to the two
         calls. ``adam``: a ``FusedAdam`` over exactly the six actor
         parameters in ``_POLICY_PARAMS`` order (the library refuses any other
-        table). Returns the loss (0-d float64 device tensor)."""
+        table). Returns the loss (0-d float64 device tensor).
+
+        ``max_grad_norm`` (None: the above, bit for bit): the gradient is
+        clipped by its global L2 norm before the step, as
+        ``adam.step(max_grad_norm=..., norm_out=...)`` does it
+        (``marlnav_ppo_actor_update_clipped``, five launches)."""
         loss = self._bind(buffer, lo, hi)
         ad, ab = adam._bind()
-        abi.check(self._lib.marlnav_ppo_actor_update_mode(
+        if max_grad_norm is None:
+            if norm_out is not None:
+                raise ValueError("norm_out needs max_grad_norm (inf records the norm only)")
+            abi.check(self._lib.marlnav_ppo_actor_update_mode(
+                ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon, self.ent_const,
+                ctypes.byref(ad), ctypes.byref(ab), self._mode, _stream(self.device)), self._lib)
+            return loss
+        g, work, out = adam._clip_args(max_grad_norm, norm_out)
+        abi.check(self._lib.marlnav_ppo_actor_update_clipped(
             ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon, self.ent_const,
-            ctypes.byref(ad), ctypes.byref(ab), self._mode, _stream(self.device)), self._lib)
+            ctypes.byref(ad), ctypes.byref(ab), self._mode, g, work, out,
+            _stream(self.device)), self._lib)
         return loss
 
-    def critic_update(self, buffer, lo, hi, adam):
+    def critic_update(self, buffer, lo, hi, adam, max_grad_norm=None, norm_out=None):
         """``critic_loss_grad`` then ``adam.step()`` as one C call
         (``marlnav_ppo_critic_update``); ``adam`` over the four critic
-        parameters. As ``actor_update``."""
+        parameters. As ``actor_update``, ``max_grad_norm`` included
+        (``marlnav_ppo_critic_update_clipped``)."""
         loss = self._bind(buffer, lo, hi, 'critic')
         ad, ab = adam._bind()
-        abi.check(self._lib.marlnav_ppo_critic_update(
+        if max_grad_norm is None:
+            if norm_out is not None:
+                raise ValueError("norm_out needs max_grad_norm (inf records the norm only)")
+            abi.check(self._lib.marlnav_ppo_critic_update(
+                ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon,
+                ctypes.byref(ad), ctypes.byref(ab), _stream(self.device)), self._lib)
+            return loss
+        g, work, out = adam._clip_args(max_grad_norm, norm_out)
+        abi.check(self._lib.marlnav_ppo_critic_update_clipped(
             ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon,
-            ctypes.byref(ad), ctypes.byref(ab), _stream(self.device)), self._lib)
+            ctypes.byref(ad), ctypes.byref(ab), g, work, out, _stream(self.device)), self._lib)
         return loss
 
 
@@ -744,7 +767,13 @@ class FusedAdam(object):
     capture time (change them, then capture again).
 
     ``state_dict()`` / ``load_state_dict()`` speak ``torch.optim.Adam``'s
-    format, so a checkpoint moves between the two in either direction."""
+    format, so a checkpoint moves between the two in either direction.
+
+    ``step(max_grad_norm=G)`` clips the gradient by its global L2 norm over
+    all parameters first, as
+    ``torch.nn.utils.clip_grad_norm_(params, G)`` before ``step()`` does. The
+    scratch of the norm's partial sums is allocated at the first such call
+    and never again, so a captured graph's pointer stays valid."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, maximize=False,
                  weight_decay=0, amsgrad=False):
@@ -784,6 +813,7 @@ class FusedAdam(object):
         self._state = torch.zeros((nstate + 7) // 8, dtype=torch.int64, device=dev)
         self._dims = abi.MarlnavAdamDims(num_tensors=len(params))
         self._bufs = abi.MarlnavAdamBuffers(state=self._state.data_ptr())
+        self._norm_work = None              # the clipped step's scratch, at first use
         for i, p in enumerate(params):
             self._dims.numel[i] = p.numel()
             self._bufs.exp_avg[i] = self.exp_avg[i].data_ptr()
@@ -825,12 +855,49 @@ class FusedAdam(object):
             b.grad[i] = g.data_ptr()
         return d, b
 
-    def step(self):
+    def _clip_args(self, max_grad_norm, norm_out, count=1, what="norm_out"):
+        """-> (max_norm, norm_work pointer, norm_out pointer or None) of a
+        clipped call; the scratch is allocated at the first one. ``norm_out``:
+        None or a contiguous float64 tensor of ``count`` elements on the
+        device. The value is checked here and again by the library."""
+        g = check_max_grad_norm(max_grad_norm)
+        if self._norm_work is None:
+            need = int(self._lib.marlnav_grad_norm_work_size(ctypes.byref(self._dims)))
+            if need < 0:
+                abi.check(need, self._lib)
+            self._norm_work = torch.empty(need, dtype=_F64, device=self.device)
+        out = None
+        if norm_out is not None:
+            if (not torch.is_tensor(norm_out) or norm_out.dtype != _F64
+                    or norm_out.device != self.device or norm_out.numel() != count
+                    or not norm_out.is_contiguous()):
+                raise ValueError(f"{what}: need a contiguous float64 tensor of {count} "
+                                 f"element(s) on {self.device}")
+            out = norm_out.data_ptr()
+        return g, self._norm_work.data_ptr(), out
+
+    def step(self, max_grad_norm=None, norm_out=None):
         """One Adam step of every parameter from its ``.grad``: one
-        ``marlnav_adam_step`` (two launches) on the current stream."""
+        ``marlnav_adam_step`` (two launches) on the current stream.
+
+        ``max_grad_norm`` (None: the above, bit for bit): ``.grad`` is first
+        scaled by ``min(1, max_grad_norm / (norm + 1e-6))``, ``norm`` the L2
+        norm over all parameters in fp64, and stays scaled afterwards, as
+        after ``clip_grad_norm_``; the norm before clipping goes to
+        ``norm_out`` (a float64 device tensor of one element) where given.
+        ``float('inf')`` records the norm and clips nothing. One
+        ``marlnav_adam_step_clipped`` (three launches), nothing synchronises;
+        the value travels as a launch argument, so a captured graph keeps it."""
         d, b = self._bind()
-        abi.check(self._lib.marlnav_adam_step(ctypes.byref(d), ctypes.byref(b),
-                                              _stream(self.device)), self._lib)
+        if max_grad_norm is None:
+            if norm_out is not None:
+                raise ValueError("norm_out needs max_grad_norm (inf records the norm only)")
+            abi.check(self._lib.marlnav_adam_step(ctypes.byref(d), ctypes.byref(b),
+                                                  _stream(self.device)), self._lib)
+            return
+        g, work, out = self._clip_args(max_grad_norm, norm_out)
+        abi.check(self._lib.marlnav_adam_step_clipped(ctypes.byref(d), ctypes.byref(b), g, work,
+                                                      out, _stream(self.device)), self._lib)
 
     def zero_grad(self, set_to_none=False):
         """Zero the gradients in place (the default here, unlike torch's: the
@@ -911,15 +978,45 @@ class FusedAdam(object):
         self._hyper()
 
 
-def _train(ppo, loss_grad, update, network, buffer, optimizer, num_epochs, batch_size, log):
+def check_max_grad_norm(max_grad_norm):
+    """``max_grad_norm`` as a float: > 0 and not NaN (``inf`` records the norm
+    and clips nothing); anything else is a ValueError."""
+    g = float(max_grad_norm)
+    if not g > 0.0:
+        raise ValueError(f"max_grad_norm={max_grad_norm} must be > 0 (inf: record the norm only)")
+    return g
+
+
+def _train(ppo, loss_grad, update, network, buffer, optimizer, num_epochs, batch_size, log,
+           max_grad_norm=None, norm_log=None):
     ppo._require(buffer)
     bounds = minibatch_bounds(len(buffer), batch_size)
     # a FusedAdam over exactly this network's parameters: one C call per
     # minibatch; any other optimiser: the two calls
     one_call = isinstance(optimizer, FusedAdam) and optimizer.covers(network)
+    if max_grad_norm is None:
+        if norm_log is not None:
+            raise ValueError("norm_log needs max_grad_norm (inf records the norms only)")
+    else:
+        check_max_grad_norm(max_grad_norm)
+        if not one_call:
+            raise ValueError("max_grad_norm needs a FusedAdam over exactly this network's "
+                             "parameters in order: the clipping is part of its step (clip any "
+                             "other optimiser's gradients yourself between loss_grad and step)")
+    cells, k = None, 0
+    if norm_log is not None:                # one allocation, an element per update
+        cells = torch.empty(int(num_epochs) * len(bounds), dtype=_F64, device=ppo.device)
     for _ in range(int(num_epochs)):
         for lo, hi in bounds:
-            if one_call:
+            if max_grad_norm is not None:
+                norm = None
+                if cells is not None:
+                    norm = cells[k]
+                    norm_log.append(norm)
+                    k += 1
+                loss = update(buffer, lo, hi, optimizer, max_grad_norm=max_grad_norm,
+                              norm_out=norm)
+            elif one_call:
                 loss = update(buffer, lo, hi, optimizer)
             else:
                 loss = loss_grad(buffer, lo, hi)
@@ -928,7 +1025,8 @@ def _train(ppo, loss_grad, update, network, buffer, optimizer, num_epochs, batch
                 log.append(loss)
 
 
-def train_actor(ppo, buffer, optimizer, num_epochs, batch_size, log=None):
+def train_actor(ppo, buffer, optimizer, num_epochs, batch_size, log=None, max_grad_norm=None,
+                norm_log=None):
     """MAPPO.train_actor (models.py:160-178): per epoch and minibatch
     (``minibatch_bounds``) the fused loss and gradients, ``optimizer.step()``,
     then ``log.append(loss)`` with the loss left on the device. ``optimizer``
@@ -939,12 +1037,19 @@ def train_actor(ppo, buffer, optimizer, num_epochs, batch_size, log=None):
     ``_POLICY_PARAMS`` order (``FusedAdam(actor.parameters(), ...)`` of the
     reference's module) the two calls of a minibatch become the one call
     ``ppo.actor_update``, with equal bits, and a whole epoch can be captured
-    in a graph."""
+    in a graph.
+
+    ``max_grad_norm`` (None: the above): every update clips its gradient by
+    the global L2 norm first (``ppo.actor_update(..., max_grad_norm=...)``,
+    DESIGN.md §16) and, with a list ``norm_log``, appends the norm before
+    clipping (0-d float64 device tensor). This needs that ``FusedAdam``: with
+    any other optimiser it is a ValueError."""
     _train(ppo, ppo.actor_loss_grad, ppo.actor_update, ppo._network_params("actor"), buffer,
-           optimizer, num_epochs, batch_size, log)
+           optimizer, num_epochs, batch_size, log, max_grad_norm, norm_log)
 
 
-def train_critic(ppo, buffer, optimizer, num_epochs, batch_size, log=None):
+def train_critic(ppo, buffer, optimizer, num_epochs, batch_size, log=None, max_grad_norm=None,
+                 norm_log=None):
     """MAPPO.train_critic (models.py:180-198), as ``train_actor``."""
     _train(ppo, ppo.critic_loss_grad, ppo.critic_update, ppo._network_params("critic"), buffer,
-           optimizer, num_epochs, batch_size, log)
+           optimizer, num_epochs, batch_size, log, max_grad_norm, norm_log)

@@ -92,7 +92,9 @@ def stats_paths(out_dir, stamp):
             'rew_log': os.path.join(l, stamp + '_mean_rews.csv'),
             'act_log': os.path.join(l, stamp + '_act_loss.csv'),
             'cri_log': os.path.join(l, stamp + '_cri_loss.csv'),
-            'epi_log': os.path.join(l, stamp + '_epi_stats.csv')}
+            'epi_log': os.path.join(l, stamp + '_epi_stats.csv'),
+            'act_gnorm_log': os.path.join(l, stamp + '_act_gnorm.csv'),
+            'cri_gnorm_log': os.path.join(l, stamp + '_cri_gnorm.csv')}
 
 
 def write_stats(logs, full_params, out_dir, stamp, plot=True):
@@ -100,8 +102,11 @@ def write_stats(logs, full_params, out_dir, stamp, plot=True):
     numbers: ``logs/<stamp>_params.json`` (indent 4, sorted keys; what json
     cannot write goes through ``str``), the three one-column CSVs (header
     ``Value``) and ``_epi_stats.csv`` (``Truncated, Collisions, Target
-    reached``), and with ``plot`` the four figures under ``plots/``. Returns
-    the paths written."""
+    reached``), and with ``plot`` the four figures under ``plots/``. Where
+    ``logs`` has ``actor_grad_norm`` / ``critic_grad_norm`` (a run with
+    ``max_grad_norm``) also ``_act_gnorm.csv`` /
+    ``_cri_gnorm.csv``, one-column like the losses; a ``logs`` without them
+    writes exactly the reference's files. Returns the paths written."""
     paths = stats_paths(out_dir, stamp)
     os.makedirs(os.path.dirname(paths['params']), exist_ok=True)
     with open(paths['params'], 'w') as f:
@@ -118,6 +123,14 @@ def write_stats(logs, full_params, out_dir, stamp, plot=True):
         writer.writerows([[epi['trunc'][i], epi['col'][i], epi['tar'][i]]
                           for i in range(len(epi['trunc']))])
     written = [paths[k] for k in ('params', 'rew_log', 'act_log', 'cri_log', 'epi_log')]
+    for key, name in (('actor_grad_norm', 'act_gnorm_log'),
+                      ('critic_grad_norm', 'cri_gnorm_log')):
+        if key in logs:
+            with open(paths[name], 'w', newline='') as f:
+                writer = csv.writer(f)
+                writer.writerow(['Value'])
+                writer.writerows([[num] for num in logs[key]])
+            written.append(paths[name])
     if not plot:
         return written
     import matplotlib
@@ -145,7 +158,8 @@ def write_stats(logs, full_params, out_dir, stamp, plot=True):
     return written + [paths[k] for k in ('rew_plot', 'act_plot', 'cri_plot', 'epi_plot')]
 
 
-def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None):
+def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None, max_grad_norm=None,
+                norm_out=None):
     """One whole ``train_actor`` (``network='actor'``) or ``train_critic``
     (``'critic'``) of the reference (models.py:160-198) over ``buffer`` as ONE
     C call, libmarlnav.so ``marlnav_ppo_train_phase``: ``num_epochs`` times
@@ -159,7 +173,16 @@ def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None):
     network's parameters in ``_POLICY_PARAMS`` order (the library refuses any
     other table). ``out``: a contiguous float64 device tensor of
     ``num_epochs * len(bounds)`` elements for the losses in update order
-    (allocated where None); returned. Nothing synchronises."""
+    (allocated where None); returned. Nothing synchronises.
+
+    ``max_grad_norm`` (None: the above, bit for bit): every update clips its
+    gradient by the global L2 norm before its Adam step, one
+    ``marlnav_ppo_train_phase_clipped``: each update is the gradient launches
+    and the clipped step's three (an actor of up to 1024 elements: two
+    launches, the norm formed inside the finish launch) and stores the bits of
+    ``ppo.actor_update(..., max_grad_norm=...)`` / ``critic_update``.
+    ``norm_out``: None or a contiguous float64 device tensor like ``out`` for
+    the norms before clipping, in update order."""
     nets = {'actor': abi.NETWORK_ACTOR, 'critic': abi.NETWORK_CRITIC,
             abi.NETWORK_ACTOR: abi.NETWORK_ACTOR, abi.NETWORK_CRITIC: abi.NETWORK_CRITIC}
     if network not in nets:
@@ -189,9 +212,18 @@ def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None):
         ppo._work = torch.empty(need, dtype=_F64, device=dev)
     b.work = ppo._work.data_ptr()
     ad, ab = adam._bind()
-    abi.check(lib.marlnav_ppo_train_phase_mode(
+    if max_grad_norm is None:
+        if norm_out is not None:
+            raise ValueError("norm_out needs max_grad_norm (inf records the norms only)")
+        abi.check(lib.marlnav_ppo_train_phase_mode(
+            nets[network], ctypes.byref(d), ctypes.byref(b), arr, B, E, ppo.epsilon,
+            ppo.ent_const, ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(), ppo._mode,
+            torch._C._cuda_getCurrentRawStream(dev.index)), lib)
+        return out
+    g, work, norms = adam._clip_args(max_grad_norm, norm_out, count=E * B)
+    abi.check(lib.marlnav_ppo_train_phase_clipped(
         nets[network], ctypes.byref(d), ctypes.byref(b), arr, B, E, ppo.epsilon, ppo.ent_const,
-        ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(), ppo._mode,
+        ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(), ppo._mode, g, work, norms,
         torch._C._cuda_getCurrentRawStream(dev.index)), lib)
     return out
 
@@ -213,6 +245,12 @@ class MAPPO(object):
     The mean-reward log and the checkpoint rule still read the reference's
     returns, so they mean the same in both modes. A value outside [0, 1] is a
     ValueError.
+
+    ``params['max_grad_norm']`` (absent or None: no clipping, today's
+    behaviour bit for bit) clips every update's gradient by its global L2
+    norm in both phases; the device logs then keep each
+    update's norm before clipping and ``logs()`` gains ``actor_grad_norm`` /
+    ``critic_grad_norm``. A value that is not > 0 is a ValueError.
 
     ``seed`` keys the policy kernel's normals (``FusedPolicy``); the modules'
     initial weights come from torch's global generator, as the reference's do.
@@ -237,6 +275,9 @@ class MAPPO(object):
         self.gae_lambda = params.get('gae_lambda')
         if self.gae_lambda is not None:
             self.gae_lambda = rollout._check_lambda(self.gae_lambda)
+        self.max_grad_norm = params.get('max_grad_norm')
+        if self.max_grad_norm is not None:
+            self.max_grad_norm = rollout.check_max_grad_norm(self.max_grad_norm)
         if env._rng != 'native' or env._init_sampler is not env._default_init_sampler:
             raise RuntimeError(f"{who} needs an env in native-RNG mode with its default init "
                                "sampler: a reference-RNG or user-assigned sampler is called on "
@@ -308,6 +349,7 @@ class MAPPO(object):
         total = params.get('num_total')
         self._cap = 0
         self._mean_log = self._epi_log = self._actor_log = self._critic_log = None
+        self._actor_norm_log = self._critic_norm_log = None    # with max_grad_norm only
         self._reserve(max(1, int(total) // (self.buffer_len * self.num_parallel)) if total else 1)
         self._logs = _empty_logs()
 
@@ -324,10 +366,16 @@ class MAPPO(object):
                torch.zeros(cap, U, dtype=_F64, device=self.device),
                torch.zeros(cap, U, dtype=_F64, device=self.device))
         old = (self._mean_log, self._epi_log, self._actor_log, self._critic_log)
+        if self.max_grad_norm is not None:
+            new += (torch.zeros(cap, U, dtype=_F64, device=self.device),
+                    torch.zeros(cap, U, dtype=_F64, device=self.device))
+            old += (self._actor_norm_log, self._critic_norm_log)
         if self._cap:
             for n, o in zip(new, old):
                 n[:self._cap].copy_(o)
-        self._mean_log, self._epi_log, self._actor_log, self._critic_log = new
+        self._mean_log, self._epi_log, self._actor_log, self._critic_log = new[:4]
+        if self.max_grad_norm is not None:
+            self._actor_norm_log, self._critic_norm_log = new[4:]
         self._cap = cap
 
     def logs(self):
@@ -335,20 +383,30 @@ class MAPPO(object):
         numbers, for the rollouts collected so far: ``epi_stats`` (``trunc`` /
         ``col`` / ``tar``, one int per rollout), ``mean_rews`` (one float per
         rollout), ``actor`` / ``critic`` (one loss per update, in order; a
-        rollout that was not trained on contributes zeros). Synchronises once:
+        rollout that was not trained on contributes zeros); with
+        ``max_grad_norm`` also ``actor_grad_norm`` / ``critic_grad_norm``, each
+        update's gradient norm before clipping, laid out as the losses.
+        Synchronises once:
         the device logs travel as one float64 tensor (the counters are exact
         below 2^53). Also kept as ``self._logs``."""
         r = self._r
         U = self._actor_log.shape[1]
+        clip = self.max_grad_norm is not None
+        norms = [self._actor_norm_log[:r].flatten(),
+                 self._critic_norm_log[:r].flatten()] if clip else []
         flat = torch.cat([self._mean_log[:r], self._epi_log[:r].to(_F64).flatten(),
                           self._actor_log[:r].flatten(), self._critic_log[:r].flatten(),
-                          self._save_state.to(_F64)]).cpu()
-        mean, epi, act, cri, save = torch.split(flat, [r, 3 * r, r * U, r * U, 2])
+                          self._save_state.to(_F64)] + norms).cpu()
+        mean, epi, act, cri, save, *norms = torch.split(
+            flat, [r, 3 * r, r * U, r * U, 2] + [r * U] * len(norms))
         epi = epi.view(r, 3).to(torch.int64).tolist()
         self._saves = (int(save[0]), int(save[1]))
         self._logs = {'epi_stats': {'trunc': [e[0] for e in epi], 'col': [e[1] for e in epi],
                                     'tar': [e[2] for e in epi]},
                       'mean_rews': mean.tolist(), 'actor': act.tolist(), 'critic': cri.tolist()}
+        if clip:
+            self._logs['actor_grad_norm'] = norms[0].tolist()
+            self._logs['critic_grad_norm'] = norms[1].tolist()
         return self._logs
 
     def save_count(self):
@@ -384,22 +442,25 @@ class MAPPO(object):
             r, 1 if self.track_best else 0, self._stream()), lib)
         self._r = r + 1
 
-    def _phase(self, network, adam, log):
+    def _phase(self, network, adam, log, norm_log):
         if self._r < 1:
             raise RuntimeError("no rollout to train on yet: call get_data() first")
         train_phase(self.ppo, self.buffer, adam, network, self.num_epochs, self.batch_size,
-                    out=log[self._r - 1])
+                    out=log[self._r - 1], max_grad_norm=self.max_grad_norm,
+                    norm_out=None if norm_log is None else norm_log[self._r - 1])
 
     def train_actor(self):
         """models.py:160-178 for the last rollout as ONE C call
         (``marlnav_ppo_train_phase``): ``num_epochs`` times the minibatches of
         ``minibatch_bounds(buffer_len, batch_size)``, each update's loss into
         the device log. Nothing is printed and nothing synchronises."""
-        self._phase(abi.NETWORK_ACTOR, self.actor_optimizer, self._actor_log)
+        self._phase(abi.NETWORK_ACTOR, self.actor_optimizer, self._actor_log,
+                    self._actor_norm_log)
 
     def train_critic(self):
         """models.py:180-198, as ``train_actor``."""
-        self._phase(abi.NETWORK_CRITIC, self.critic_optimizer, self._critic_log)
+        self._phase(abi.NETWORK_CRITIC, self.critic_optimizer, self._critic_log,
+                    self._critic_norm_log)
 
     def repeat(self):
         """One pass of the reference's loop body (__main__.py:25-27):

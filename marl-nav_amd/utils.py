@@ -173,7 +173,12 @@ def set_model_params(args, device):
         raise ValueError('num_total should be divisible with (buffer_len * num_parallel).')
     obs_size = 2 + 2 * args.num_obstacles + 2 * (args.num_agents - 1)
     # marlnav_amd only: the GAE(lambda) advantage mode, present only when asked for
-    gae = {} if getattr(args, 'gae_lambda', None) is None else {'gae_lambda': args.gae_lambda}
+    extra = {} if getattr(args, 'gae_lambda', None) is None else {'gae_lambda': args.gae_lambda}
+    # marlnav_amd only: global-norm gradient clipping, present only when asked for
+    if getattr(args, 'max_grad_norm', None) is not None:
+        if not float(args.max_grad_norm) > 0.0:
+            raise ValueError(f"max_grad_norm={args.max_grad_norm} must be > 0.")
+        extra['max_grad_norm'] = args.max_grad_norm
     return {
         'actor': {'input_size': obs_size, 'hidden_size': args.hidden_size},
         'critic': {'input_size': obs_size * args.num_agents, 'hidden_size': args.hidden_size},
@@ -191,7 +196,7 @@ def set_model_params(args, device):
         'action_size': 2,
         'normalizer': set_normalizer_params(args, device),
         'scaler': set_scaler_params(args, device),
-        **gae,
+        **extra,
     }
 
 
