@@ -732,6 +732,72 @@ int marlnav_ppo_train_phase_clipped(int network, const MarlnavPpoDims *dims,
 #define MARLNAV_CLIP_FOLD_DEFAULT 1
 int marlnav_debug_clip_fold(int on);
 
+/* Actor diagnostics and the target-KL stop, on the device.
+ * The diagnostic form of the actor's gradient launches adds two fp64 sums to
+ * the pass (through the reduction that carries the loss sums) and writes one
+ * row of MARLNAV_DIAG_ROW doubles per update:
+ *   [0] surrogate_mean  the clipped-surrogate mean (the loss's first term)
+ *   [1] entropy_mean    the entropy's fp64 mean;
+ *                       loss == [0] + (double)((float)ent_const * (float)[1])
+ *   [2] approx_kl       mean of ((double)ratio - 1.0) - (double)lr per row, the
+ *                       k3 estimator (r - 1) - log r with lr the fp32
+ *                       new_log_prob - log_prob whose expf is the fp32 ratio
+ *   [3] clip_frac       the fraction of rows with ratio outside the fp32 bounds
+ *                       [1 - epsilon, 1 + epsilon] (a NaN ratio is outside)
+ *   [4] status          0.0 applied, 1.0 the update that raised the stop,
+ *                       2.0 an update behind the stop
+ * loss and every .grad element carry the bits of the plain call: the new
+ * accumulators touch none of the existing ones. The pass's partial rows are two
+ * doubles longer: `work` has marlnav_ppo_diag_work_size(dims) doubles, for the
+ * phase marlnav_ppo_train_diag_work_size(dims, bounds, num_batches) (never
+ * less than the plain queries' values; negative on bad arguments).
+ *
+ * marlnav_ppo_actor_grad_diag: marlnav_ppo_actor_grad_mode plus `diag` (device,
+ * 8-byte aligned). No stop: status is 0.
+ *
+ * marlnav_ppo_train_phase_monitored: the actor's marlnav_ppo_train_phase_mode /
+ * _clipped with the row of every update in diag_log and the stop.
+ *   network    MARLNAV_NETWORK_ACTOR; the critic is refused
+ *   max_norm   as for _clipped, or MARLNAV_MAX_NORM_NONE: no clip, the two
+ *              launches of marlnav_adam_step; norm_work and norm_log NULL then
+ *   target_kl  > 0; +inf: monitor only, no update ever stops (status 0 always)
+ *   diag_log   device, num_epochs * num_batches rows, update k writes row k
+ *   stop       device, 2 int64: {flag, stopped_at}. The call's first launch
+ *              resets it to {0, -1}; whatever it held before is ignored
+ * In the finish launch of update k one thread evaluates !(approx_kl <=
+ * target_kl), so a NaN KL stops. The comparison is with target_kl itself:
+ * a caller who wants Stable-Baselines3's rule passes 1.5 x its target. The
+ * stop sits before the optimiser step, as there:
+ *   status 0  loss, row and .grad stored; the Adam step (clipped where asked)
+ *             applied. Bit for bit the plain phase's update.
+ *   status 1  loss, row and .grad stored; stop = {1, k}; NO Adam step:
+ *             parameters, moments, count, step scalars, the clip's coefficient
+ *             cell and norm_log[k] stay as they were
+ *   status 2  every later update of the call: loss_log[k] and row k are NaN but
+ *             for status; .grad, parameters, moments, count, norm_log[k] stay
+ * Every launch of an update behind the stop reads the flag, which an earlier
+ * launch wrote, and returns: such an update costs its launches, not work. No
+ * atomics and no host read; a captured graph replays the decision. An update
+ * is the two gradient launches and the gated forms of marlnav_adam_step's two
+ * (or _clipped's three); nothing is folded. Everything is validated before the
+ * first launch (MARLNAV_EINVAL, the message names the field). */
+#define MARLNAV_DIAG_ROW 5
+#define MARLNAV_MAX_NORM_NONE 0.0
+int64_t marlnav_ppo_diag_work_size(const MarlnavPpoDims *dims);
+int64_t marlnav_ppo_train_diag_work_size(const MarlnavPpoDims *dims, const int64_t *bounds,
+                                         int64_t num_batches);
+int marlnav_ppo_actor_grad_diag(const MarlnavPpoDims *dims, const MarlnavPpoBuffers *bufs,
+                                double epsilon, double ent_const, int advantage_mode,
+                                double *diag, void *stream);
+int marlnav_ppo_train_phase_monitored(int network, const MarlnavPpoDims *dims,
+                                      const MarlnavPpoBuffers *bufs, const int64_t *bounds,
+                                      int64_t num_batches, int64_t num_epochs, double epsilon,
+                                      double ent_const, const MarlnavAdamDims *adam_dims,
+                                      const MarlnavAdamBuffers *adam_bufs, double *loss_log,
+                                      int advantage_mode, double max_norm, double *norm_work,
+                                      double *norm_log, double target_kl, double *diag_log,
+                                      int64_t *stop, void *stream);
+
 /* The checkpoint rule of MAPPO.get_data (models.py:127-129) on the device: if
  * *mean_rew > *max_rew (fp64; a NaN mean is not greater), copy src[i] to
  * dst[i] (numel[i] fp32 elements, any 4-byte alignment, i < num_tensors <=

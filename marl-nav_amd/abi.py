@@ -169,6 +169,8 @@ ADVANTAGE_REFERENCE, ADVANTAGE_ENV = 0, 1
 # what marlnav_critic_values dereferences
 CRITIC_VALUES_REQUIRED = ("obs_norm",) + POLICY_WEIGHT_FIELDS[6:] + ("values",)
 SNAPSHOT_MAX_TENSORS = 10
+DIAG_ROW = 5            # surrogate mean, entropy mean, approximate KL, clip fraction, status
+MAX_NORM_NONE = 0.0     # marlnav_ppo_train_phase_monitored without a clip
 
 EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_formation_obs",
            "marlnav_counter_slots", "marlnav_counters_total",
@@ -185,6 +187,8 @@ EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_for
            "marlnav_grad_norm_work_size", "marlnav_adam_step_clipped",
            "marlnav_ppo_actor_update_clipped", "marlnav_ppo_critic_update_clipped",
            "marlnav_ppo_train_phase_clipped", "marlnav_debug_clip_fold",
+           "marlnav_ppo_actor_grad_diag", "marlnav_ppo_train_phase_monitored",
+           "marlnav_ppo_diag_work_size", "marlnav_ppo_train_diag_work_size",
            "marlnav_last_error", "marlnav_abi_version",
            "marlnav_debug_force_family", "marlnav_debug_last_family",
            "marlnav_debug_acos_range", "marlnav_debug_fastdiv_check")
@@ -298,6 +302,19 @@ def _declare(lib):
                                                     adam_dims_p, adam_bufs_p, _P, c.c_int,
                                                     c.c_double, _P, _P, _P]
     lib.marlnav_ppo_train_phase_clipped.restype = c.c_int
+    # the diagnostic forms: ..., diag / ..., target_kl, diag_log, stop, stream
+    lib.marlnav_ppo_diag_work_size.argtypes = [ppo_dims_p]
+    lib.marlnav_ppo_diag_work_size.restype = c.c_int64
+    lib.marlnav_ppo_train_diag_work_size.argtypes = [ppo_dims_p, i64_p, c.c_int64]
+    lib.marlnav_ppo_train_diag_work_size.restype = c.c_int64
+    lib.marlnav_ppo_actor_grad_diag.argtypes = [ppo_dims_p, ppo_bufs_p, c.c_double, c.c_double,
+                                                c.c_int, _P, _P]
+    lib.marlnav_ppo_actor_grad_diag.restype = c.c_int
+    lib.marlnav_ppo_train_phase_monitored.argtypes = [c.c_int, ppo_dims_p, ppo_bufs_p, i64_p,
+                                                      c.c_int64, c.c_int64, c.c_double, c.c_double,
+                                                      adam_dims_p, adam_bufs_p, _P, c.c_int,
+                                                      c.c_double, _P, _P, c.c_double, _P, _P, _P]
+    lib.marlnav_ppo_train_phase_monitored.restype = c.c_int
     lib.marlnav_debug_clip_fold.argtypes = [c.c_int]
     lib.marlnav_debug_clip_fold.restype = c.c_int
     lib.marlnav_last_error.argtypes = []

@@ -34,6 +34,18 @@ global L2 norm and adds the two ``_gnorm.csv`` logs; it
 composes with ``--gae-lambda``.
 
     python -m marlnav_amd --train --max-grad-norm 0.5 -np 4096 -bl 16 -bs 8 -ne 4 -nt 1048576
+
+``--target-kl K`` with ``--train`` abandons the remaining actor updates of a
+rollout once an update's approximate KL divergence from the rollout policy
+exceeds K (decided on the device, before that update's
+optimiser step; Stable-Baselines3 compares with 1.5 K, so pass 1.5 times its
+value for its rule). ``--log-diagnostics`` records every actor update's
+approximate KL, clip fraction, entropy and surrogate without stopping. Either
+adds ``_act_kl.csv``, ``_act_clipfrac.csv``, ``_act_entropy.csv``,
+``_act_stop.csv`` and the figure ``_act_kl.png``; both compose with
+``--gae-lambda`` and ``--max-grad-norm``.
+
+    python -m marlnav_amd --train --target-kl 0.02 -np 4096 -bl 16 -bs 8 -ne 4 -nt 1048576
 """
 import argparse
 import sys
@@ -113,6 +125,12 @@ def build_parser():
     a('--max-grad-norm', type=float, default=None, metavar='G',
       help='with --train: clip every update\'s gradient to the global L2 norm G > 0, as '
            'clip_grad_norm_ does (default: no clipping)')
+    a('--target-kl', type=float, default=None, metavar='K',
+      help='with --train: stop a rollout\'s actor updates once the approximate KL divergence '
+           'from the rollout policy exceeds K > 0 (default: no stop)')
+    a('--log-diagnostics', action='store_true',
+      help='with --train: log every actor update\'s approximate KL, clip fraction, entropy '
+           'and surrogate')
     a('--out-dir', default='.', help='with --train: where weights/, logs/ and plots/ go')
     a('--plot-dir', default='plots', help='directory of the saved figures')
     a('--no-plots', action='store_true', help='skip the figures, print the series')

@@ -91,9 +91,23 @@ struct AdamArgs {
     int maximize;
 };
 
-__global__ void __launch_bounds__(64) adam_advance(AdamState *s, double lr, double beta1,
-                                                    double beta2)
+// The kernels below take a trailing pack: empty, they are the kernels as they
+// were; with one `const int64_t *` (the stop flag of the monitored actor
+// phase) every thread first reads the flag, which an earlier
+// launch wrote and no thread of these launches writes, and returns where it
+// is set: the gated step of an update that raised the stop, or lies behind it,
+// touches nothing.
+template <class... G>
+__device__ __forceinline__ bool gate_closed(G... flag)
 {
+    return ((*flag != 0) || ... || false);
+}
+
+template <class... G>
+__global__ void __launch_bounds__(64) adam_advance(AdamState *s, double lr, double beta1,
+                                                    double beta2, G... gate)
+{
+    if (gate_closed(gate...)) return;
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     marlnav_adam::adam_advance_one(s, lr, beta1, beta2);
 }
@@ -102,9 +116,10 @@ __global__ void __launch_bounds__(64) adam_advance(AdamState *s, double lr, doub
 // coefficient that adam_advance_clip published, stored back into .grad, and
 // the element is updated from that stored value. The unclipped instantiation
 // is the kernel of marlnav_adam_step.
-template <bool kClip>
-__global__ void __launch_bounds__(kThreads) adam_apply(AdamArgs a)
+template <bool kClip, class... G>
+__global__ void __launch_bounds__(kThreads) adam_apply(AdamArgs a, G... gate)
 {
+    if (gate_closed(gate...)) return;
     const int64_t item = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (item >= a.item_end[kSlots - 1]) return;
     // the slot of this item: a chain of selects over the by-value table
@@ -179,9 +194,11 @@ __global__ void __launch_bounds__(kThreads) adam_apply(AdamArgs a)
 // thread = item as adam_apply; a thread's fp64 sum of its <= 4 squares in
 // element order (0 past the table's last item), then block_sum; block b's
 // partial goes to partials[b]. Reads .grad only.
-__global__ void __launch_bounds__(kThreads) grad_sqsum(AdamArgs a, double *partials)
+template <class... G>
+__global__ void __launch_bounds__(kThreads) grad_sqsum(AdamArgs a, double *partials, G... gate)
 {
     __shared__ double sh[kWaves];
+    if (gate_closed(gate...)) return;  // uniform: ahead of block_sum's barriers
     const int64_t item = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     double acc = 0.0;
     if (item < a.item_end[kSlots - 1]) {
@@ -222,13 +239,16 @@ __global__ void __launch_bounds__(kThreads) grad_sqsum(AdamArgs a, double *parti
 // writes the norm and, last, advances the count (no other thread writes, and
 // nothing written here is read in this launch except through block_sum's
 // barrier).
+template <class... G>
 __global__ void __launch_bounds__(kThreads) adam_advance_clip(AdamState *s, double lr,
                                                               double beta1, double beta2,
                                                               const double *partials,
                                                               int64_t num_partials,
-                                                              double max_norm, double *norm_out)
+                                                              double max_norm, double *norm_out,
+                                                              G... gate)
 {
     __shared__ double sh[kWaves];
+    if (gate_closed(gate...)) return;
     if (blockIdx.x != 0) return;
     double acc = 0.0;
     for (int64_t i = threadIdx.x; i < num_partials; i += kThreads) acc += partials[i];
@@ -320,9 +340,10 @@ int check_clip(double max_norm, const void *norm_work, const void *norm_out, con
 }
 
 // checked arguments only. clip NULL: the two launches of marlnav_adam_step;
-// given: the three of marlnav_adam_step_clipped.
+// given: the three of marlnav_adam_step_clipped. gate: the same launches in
+// their gated forms (the monitored actor phase).
 int enqueue_adam(const MarlnavAdamDims *d, const MarlnavAdamBuffers *b, hipStream_t s,
-                 const ClipArgs *clip = nullptr)
+                 const ClipArgs *clip = nullptr, const int64_t *gate = nullptr)
 {
     AdamArgs a;
     int64_t items = 0;
@@ -352,15 +373,29 @@ int enqueue_adam(const MarlnavAdamDims *d, const MarlnavAdamBuffers *b, hipStrea
     a.maximize = d->maximize;
     // items <= 2^38 + 8: the grid fits 31 bits
     const dim3 grid((unsigned)((items + kThreads - 1) / kThreads));
-    if (clip) {
-        hipLaunchKernelGGL(grad_sqsum, grid, dim3(kThreads), 0, s, a, clip->norm_work);
+    if (gate && clip) {
+        hipLaunchKernelGGL(grad_sqsum, grid, dim3(kThreads), 0, s, a, clip->norm_work, gate);
         hipLaunchKernelGGL(adam_advance_clip, dim3(1), dim3(kThreads), 0, s, state, d->lr,
-                           d->beta1, d->beta2, clip->norm_work, (int64_t)grid.x, clip->max_norm,
-                           clip->norm_out);
+                           d->beta1, d->beta2, (const double *)clip->norm_work, (int64_t)grid.x,
+                           clip->max_norm, clip->norm_out, gate);
+        hipLaunchKernelGGL(adam_apply<true>, grid, dim3(kThreads), 0, s, a, gate);
+        return launch_status();
+    }
+    if (gate) {
+        hipLaunchKernelGGL(adam_advance, dim3(1), dim3(64), 0, s, state, d->lr, d->beta1,
+                           d->beta2, gate);
+        hipLaunchKernelGGL(adam_apply<false>, grid, dim3(kThreads), 0, s, a, gate);
+        return launch_status();
+    }
+    if (clip) {
+        hipLaunchKernelGGL(grad_sqsum<>, grid, dim3(kThreads), 0, s, a, clip->norm_work);
+        hipLaunchKernelGGL(adam_advance_clip<>, dim3(1), dim3(kThreads), 0, s, state, d->lr,
+                           d->beta1, d->beta2, (const double *)clip->norm_work, (int64_t)grid.x,
+                           clip->max_norm, clip->norm_out);
         hipLaunchKernelGGL(adam_apply<true>, grid, dim3(kThreads), 0, s, a);
         return launch_status();
     }
-    hipLaunchKernelGGL(adam_advance, dim3(1), dim3(64), 0, s, state, d->lr, d->beta1, d->beta2);
+    hipLaunchKernelGGL(adam_advance<>, dim3(1), dim3(64), 0, s, state, d->lr, d->beta1, d->beta2);
     hipLaunchKernelGGL(adam_apply<false>, grid, dim3(kThreads), 0, s, a);
     return launch_status();
 }
@@ -576,8 +611,10 @@ void minibatch(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, int64_t lo, 
 
 }  // namespace
 
-extern "C" int64_t marlnav_ppo_train_work_size(const MarlnavPpoDims *d, const int64_t *bounds,
-                                               int64_t num_batches)
+namespace {
+
+int64_t train_work_size(const MarlnavPpoDims *d, const int64_t *bounds, int64_t num_batches,
+                        int64_t (*one)(const MarlnavPpoDims *))
 {
     if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
     const int rc = check_bounds(d, bounds, num_batches);
@@ -586,23 +623,36 @@ extern "C" int64_t marlnav_ppo_train_work_size(const MarlnavPpoDims *d, const in
     for (int64_t j = 0; j < num_batches; ++j) {
         MarlnavPpoDims md = *d;
         md.num_steps = bounds[2 * j + 1] - bounds[2 * j];
-        const int64_t w = marlnav_ppo_work_size(&md);
+        const int64_t w = one(&md);
         if (w < 0) return w;
         if (w > need) need = w;
     }
     return need;
 }
 
+}  // namespace
+
+extern "C" int64_t marlnav_ppo_train_work_size(const MarlnavPpoDims *d, const int64_t *bounds,
+                                               int64_t num_batches)
+{
+    return train_work_size(d, bounds, num_batches, marlnav_ppo_work_size);
+}
+
+extern "C" int64_t marlnav_ppo_train_diag_work_size(const MarlnavPpoDims *d,
+                                                    const int64_t *bounds, int64_t num_batches)
+{
+    return train_work_size(d, bounds, num_batches, marlnav_ppo_diag_work_size);
+}
+
 namespace {
 
-// clip NULL: marlnav_ppo_train_phase_mode; given: its _clipped form, whose
-// norm_out is the norm_log (update k writes [k]) or NULL
-int train_phase(int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
-                const int64_t *bounds, int64_t num_batches, int64_t num_epochs, double epsilon,
-                double ent_const, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
-                double *loss_log, int advantage_mode, const ClipArgs *clip, void *stream)
+// every check of a phase call before its first launch; clip as for train_phase
+int check_train_phase(int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                      const int64_t *bounds, int64_t num_batches, int64_t num_epochs,
+                      double epsilon, double ent_const, const MarlnavAdamDims *ad,
+                      const MarlnavAdamBuffers *ab, double *loss_log, int advantage_mode,
+                      const ClipArgs *clip, void *stream)
 {
-    // ---- every check before the first launch
     if (network != MARLNAV_NETWORK_ACTOR && network != MARLNAV_NETWORK_CRITIC)
         return failf(MARLNAV_EINVAL, "train: network=%d must be MARLNAV_NETWORK_ACTOR or _CRITIC", network);
     if (advantage_mode != MARLNAV_ADVANTAGE_REFERENCE && advantage_mode != MARLNAV_ADVANTAGE_ENV)
@@ -656,6 +706,21 @@ int train_phase(int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b
                                        ab, stream, 1);
         if (rc) return rc;
     }
+    return 0;
+}
+
+// clip NULL: marlnav_ppo_train_phase_mode; given: its _clipped form, whose
+// norm_out is the norm_log (update k writes [k]) or NULL
+int train_phase(int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                const int64_t *bounds, int64_t num_batches, int64_t num_epochs, double epsilon,
+                double ent_const, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
+                double *loss_log, int advantage_mode, const ClipArgs *clip, void *stream)
+{
+    int rc = check_train_phase(network, d, b, bounds, num_batches, num_epochs, epsilon, ent_const,
+                               ad, ab, loss_log, advantage_mode, clip, stream);
+    if (rc) return rc;
+    MarlnavPpoDims md;
+    MarlnavPpoBuffers mb;
     // ---- num_epochs x num_batches updates, epoch-major: two launches for the
     // actor, two or three for the critic, each with the Adam step inside (a
     // large actor keeps the four launches of marlnav_ppo_actor_update)
@@ -732,6 +797,62 @@ extern "C" int marlnav_ppo_train_phase(int network, const MarlnavPpoDims *d,
     return marlnav_ppo_train_phase_mode(network, d, b, bounds, num_batches, num_epochs, epsilon,
                                         ent_const, ad, ab, loss_log, MARLNAV_ADVANTAGE_REFERENCE,
                                         stream);
+}
+
+// =========================================================================
+// the monitored actor phase
+// =========================================================================
+__attribute__((visibility("hidden"))) int marlnav_internal_ppo_actor_diag(
+    const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon, double ent_const,
+    int advantage_mode, double *diag_row, int64_t *stop, double target_kl, int64_t k, void *stream);
+
+extern "C" int marlnav_ppo_train_phase_monitored(
+    int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, const int64_t *bounds,
+    int64_t num_batches, int64_t num_epochs, double epsilon, double ent_const,
+    const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, double *loss_log, int advantage_mode,
+    double max_norm, double *norm_work, double *norm_log, double target_kl, double *diag_log,
+    int64_t *stop, void *stream)
+{
+    // ---- every check before the first launch
+    if (network == MARLNAV_NETWORK_CRITIC)
+        return marlnav_internal_fail(MARLNAV_EINVAL,
+                                     "train: the monitored phase is the actor's; network is "
+                                     "MARLNAV_NETWORK_CRITIC");
+    const bool clipped = max_norm != MARLNAV_MAX_NORM_NONE;  // a NaN is refused by check_clip
+    if (!clipped && (norm_work || norm_log))
+        return marlnav_internal_fail(MARLNAV_EINVAL,
+                                     "clip: norm_work and norm_log must be NULL with "
+                                     "max_norm = MARLNAV_MAX_NORM_NONE");
+    const ClipArgs clip = {max_norm, norm_work, norm_log};
+    int rc = check_train_phase(network, d, b, bounds, num_batches, num_epochs, epsilon, ent_const,
+                               ad, ab, loss_log, advantage_mode, clipped ? &clip : nullptr, stream);
+    if (rc) return rc;
+    if (!(target_kl > 0.0))  // a NaN is not greater
+        return failf(MARLNAV_EINVAL, "train: target_kl=%g must be > 0 (+inf: monitor only)",
+                     target_kl);
+    if (!diag_log) return marlnav_internal_fail(MARLNAV_EINVAL, "train: diag_log is NULL");
+    if (addr(diag_log) & 7u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "train: diag_log must be 8-byte aligned");
+    if (!stop) return marlnav_internal_fail(MARLNAV_EINVAL, "train: stop is NULL");
+    if (addr(stop) & 7u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "train: stop must be 8-byte aligned");
+    // ---- num_epochs x num_batches updates: the diagnostic gradient launches,
+    // whose finish publishes the flag, then the gated Adam launches (2, or 3
+    // with a clip). Nothing is folded: an update that stops must not step.
+    MarlnavPpoDims md;
+    MarlnavPpoBuffers mb;
+    int64_t k = 0;
+    for (int64_t e = 0; e < num_epochs; ++e)
+        for (int64_t j = 0; j < num_batches; ++j, ++k) {
+            minibatch(d, b, bounds[2 * j], bounds[2 * j + 1], loss_log + k, &md, &mb);
+            rc = marlnav_internal_ppo_actor_diag(&md, &mb, epsilon, ent_const, advantage_mode,
+                                                 diag_log + MARLNAV_DIAG_ROW * k, stop, target_kl, k, stream);
+            if (rc) return rc;
+            const ClipArgs ck = {max_norm, norm_work, norm_log ? norm_log + k : nullptr};
+            rc = enqueue_adam(ad, ab, (hipStream_t)stream, clipped ? &ck : nullptr, stop);
+            if (rc) return rc;
+        }
+    return 0;
 }
 
 extern "C" int marlnav_debug_clip_fold(int on)

@@ -41,7 +41,9 @@
 // marlnav_ppo_*_grad. With AdvArgs a pass kernel's last act is one thread
 // advancing Adam's step count; with FoldArgs a finish kernel applies the Adam
 // element update to every gradient element it has stored (the training
-// phase call of marlnav_adam.hip).
+// phase call of marlnav_adam.hip). With DiagArgs the actor's two
+// kernels also form the update's diagnostics and decide the target-KL stop
+// (marlnav_ppo_actor_grad_diag, marlnav_ppo_train_phase_monitored, §17).
 //
 // Determinism: no atomics, every sum in a fixed order that depends on the
 // dims only. Built with -ffp-contract=off: every FMA below is explicit.
@@ -177,6 +179,37 @@ struct is_clip_fold<ClipFoldArgs> {
 // 16 blocks of 256 items: far above what the 1024-element fold limit needs (2)
 constexpr int kClipFoldMaxBlocks = 16;
 
+// The diagnostic variant: actor_pass adds the k3 KL terms and
+// the count of rows whose ratio left the clip range to its partial row (two
+// more fp64 sums), actor_finish writes the update's row of five doubles
+// [surrogate mean, entropy mean, approximate KL, clip fraction, status] and,
+// where `stop` is given, decides the stop. stop[0] is the flag, stop[1] the
+// update that raised it. Datum by datum: the flag is written by thread 0 of
+// the first update's pass launch (the reset, which no thread of that update
+// reads: `first`) and by thread 0 of a finish launch behind that block's
+// barriers; it is read at the top of every later launch of the phase, the
+// finish block's own reads ahead of its first barrier. Stream order covers
+// the rest: no atomics, no host read.
+struct DiagArgs {
+    double *diag;      // the update's row of kDiagRow doubles
+    int64_t *stop;     // {flag, stopped_at}, or NULL: no stop (status 0)
+    double target_kl;  // +inf: monitor only
+    int64_t k;         // the update's index in its phase call
+    int first;         // the phase's first update: resets stop, reads no flag
+};
+constexpr int kDiagSums = 2;  // KL sum, outside count: columns behind the loss sums
+constexpr int kDiagRow = 5;
+constexpr int kDiagGroups = kThreads / kDiagSums;
+
+template <class... X>
+struct is_diag {
+    static constexpr bool value = false;
+};
+template <>
+struct is_diag<DiagArgs> {
+    static constexpr bool value = true;
+};
+
 // p[0] + p[stride] + ... (n terms) in that order, the loads of eight terms
 // issued before their adds (a rolled loop pays one memory round trip per term)
 __device__ __forceinline__ double sum_strided(const double *__restrict__ p, int64_t n,
@@ -221,6 +254,12 @@ enum { kPairReference = 0, kPairEnv = 1 };
 template <int PAIRING, class... X>
 __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
 {
+    constexpr bool kDiag = is_diag<X...>::value;
+    if constexpr (kDiag) {
+        // an update behind the stop costs its launches only (uniform per grid)
+        const DiagArgs &dg = only(x...);
+        if (dg.stop && !dg.first && dg.stop[0] != 0) return;
+    }
     const int D = g.D, H = g.H;
     const int ncol = D + 1;
     extern __shared__ __attribute__((aligned(16))) double s_dyn_d[];
@@ -272,6 +311,7 @@ __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
     for (int i = 0; i < kActorColsPerThread; ++i)
         acc[i][0] = acc[i][1] = acc[i][2] = acc[i][3] = 0.0;
     double sum_surr = 0.0, sum_ent = 0.0;
+    double sum_kl = 0.0, sum_out = 0.0;  // kDiag only
 
     const int64_t M = g.M, N = g.N;
     const double inv_m = 1.0 / (double)M;
@@ -309,7 +349,8 @@ __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
             const float ld = logf(v0) + logf(v1);
             const float lp = __builtin_fmaf(-0.5f, q0 + q1, __builtin_fmaf(-0.5f, ld, -kLog2Pi));
             const float ent = __builtin_fmaf(0.5f, ld, 1.0f + kLog2Pi);
-            const float ratio = expf(lp - g.b.log_probs[row]);
+            const float lr = lp - g.b.log_probs[row];
+            const float ratio = expf(lr);
             double adv;
             if constexpr (PAIRING == kPairEnv) {
                 // row / A: the row's own env row, tile = tile_n A + tile_a
@@ -325,6 +366,12 @@ __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
             sum_surr += sb < sa ? sb : sa;
             sum_ent += (double)ent;
             const bool inside = ratio >= g.clip_lo && ratio <= g.clip_hi;
+            if constexpr (kDiag) {
+                // k3, (r - 1) - log r, in fp64 from the fp32 ratio and log
+                // ratio: in fp32 the subtraction cancels to nothing
+                sum_kl += ((double)ratio - 1.0) - (double)lr;
+                sum_out += inside ? 0.0 : 1.0;
+            }
             const float g_ratio = (inside || sa < sb) ? (float)(adv * inv_m) : 0.0f;
             const float g_lp = g_ratio * ratio;
             const float g_mu0 = g_lp * (d0 * iv0), g_mu1 = g_lp * (d1 * iv1);
@@ -364,7 +411,8 @@ __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
     }
 
     // ---- block partials: the slices of a column added in slice order
-    double *__restrict__ out = g.b.work + (int64_t)blockIdx.x * actor_stride(D);
+    double *__restrict__ out =
+        g.b.work + (int64_t)blockIdx.x * (actor_stride(D) + (kDiag ? kDiagSums : 0));
     if (slices == 1) {
         // 128 < ncol < 256: the threads t >= ncol own nothing (us == 1) and
         // must not store their zeros over the owners' columns
@@ -402,7 +450,19 @@ __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
         out[4 * ncol] = bs;
         out[4 * ncol + 1] = bent;
     }
-    if constexpr (sizeof...(X) != 0) {
+    if constexpr (kDiag) {
+        const double bkl = block_sum(sum_kl, s_red);
+        const double bout = block_sum(sum_out, s_red);
+        const DiagArgs &dg = only(x...);
+        if (t == 0) {
+            out[4 * ncol + 2] = bkl;
+            out[4 * ncol + 3] = bout;
+            if (dg.stop && dg.first && blockIdx.x == 0) {
+                dg.stop[0] = 0;
+                dg.stop[1] = -1;
+            }
+        }
+    } else if constexpr (sizeof...(X) != 0) {
         // the count of the update this launch belongs to: one thread, read by
         // no thread of this launch, by every thread of the finish launch. Last
         // in the kernel, where nothing else is live: its pow() at the start
@@ -423,13 +483,29 @@ __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
 template <class... X>
 __global__ void __launch_bounds__(kThreads) actor_finish(PpoArgs g, X... x)
 {
+    constexpr bool kDiag = is_diag<X...>::value;
     const int D = g.D, H = g.H, ncol = D + 1;
     const int nS = 4 * ncol + 2;
     extern __shared__ __attribute__((aligned(16))) double s_fin[];
     double *s_S = s_fin;          // [r][c] totals, then the two loss sums
     double *s_grp = s_fin + nS;   // group partials [grp][nS] when nS < kThreads
     const int t = threadIdx.x;
-    const int64_t stride = actor_stride(D);
+    if constexpr (kDiag) {
+        // behind the stop: the update's log cells say so and nothing else is
+        // touched. Read ahead of the block's first barrier; thread 0's write
+        // of the flag below is behind it.
+        const DiagArgs &dg = only(x...);
+        if (dg.stop && !dg.first && dg.stop[0] != 0) {
+            if (t == 0) {
+                const double nan = __builtin_nan("");
+                g.b.loss[0] = nan;
+                for (int i = 0; i < kDiagRow - 1; ++i) dg.diag[i] = nan;
+                dg.diag[kDiagRow - 1] = 2.0;
+            }
+            return;
+        }
+    }
+    const int64_t stride = actor_stride(D) + (kDiag ? kDiagSums : 0);
     const double *__restrict__ work = g.b.work;
     const int groups = nS >= kThreads ? 1 : kThreads / nS;
     if (groups == 1) {
@@ -449,7 +525,40 @@ __global__ void __launch_bounds__(kThreads) actor_finish(PpoArgs g, X... x)
     }
     __syncthreads();
 
-    if (t == 0) {
+    if constexpr (kDiag) {
+        // the two diagnostic columns, whatever D: thread = (column t & 1, group
+        // t >> 1 of 128) adds its blocks grp, grp + 128, ... in that order,
+        // block_sum adds a column's 128 group sums (the other column's
+        // threads add zeros)
+        const DiagArgs &dg = only(x...);
+        double *s_red = s_fin + (size_t)nS * (1 + (groups > 1 ? groups : 0));
+        const int c = t & 1, grp = t >> 1;
+        const int64_t n =
+            grp < g.nblocks ? (g.nblocks - grp + kDiagGroups - 1) / kDiagGroups : 0;
+        const double part = sum_strided(work + grp * stride + nS + c, n, kDiagGroups * stride);
+        const double tot_kl = block_sum(c == 0 ? part : 0.0, s_red);
+        const double tot_out = block_sum(c == 1 ? part : 0.0, s_red);
+        if (t == 0) {
+            // the loss as below, the entropy's fp64 quotient kept for the row
+            const double m = (double)g.M;
+            const double clip_loss = s_S[4 * ncol] / m;
+            const double ent_q = s_S[4 * ncol + 1] / m;
+            const float ent_mean = (float)ent_q;
+            g.b.loss[0] = clip_loss + (double)(g.ent_f * ent_mean);
+            const double kl = tot_kl / m;
+            // !(kl <= target): a NaN KL stops; target = +inf is monitor only
+            const bool stop_now = dg.stop && dg.target_kl < __builtin_inf() && !(kl <= dg.target_kl);
+            dg.diag[0] = clip_loss;
+            dg.diag[1] = ent_q;
+            dg.diag[2] = kl;
+            dg.diag[3] = tot_out / m;
+            dg.diag[4] = stop_now ? 1.0 : 0.0;
+            if (stop_now) {
+                dg.stop[0] = 1;
+                dg.stop[1] = dg.k;
+            }
+        }
+    } else if (t == 0) {
         // clip mean in fp64; entropy mean rounded to fp32 and scaled in fp32
         const double clip_loss = s_S[4 * ncol] / (double)g.M;
         const float ent_mean = (float)(s_S[4 * ncol + 1] / (double)g.M);
@@ -546,7 +655,7 @@ __global__ void __launch_bounds__(kThreads) actor_finish(PpoArgs g, X... x)
             else
                 clip_fold_element(f, 1, j, gp[1], coef, c);
         }
-    } else if constexpr (sizeof...(X) != 0) {
+    } else if constexpr (sizeof...(X) != 0 && !kDiag) {
         __syncthreads();
         const FoldArgs &f = only(x...);
         const AdamScalars c = fold_scalars(f);
@@ -986,14 +1095,17 @@ PpoArgs make_args(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b)
 
 }  // namespace
 
-extern "C" int64_t marlnav_ppo_work_size(const MarlnavPpoDims *d)
+namespace {
+
+// diag: the actor's partial rows carry the diagnostic variant's two columns
+int64_t work_size(const MarlnavPpoDims *d, bool diag)
 {
     const int rc = check_dims(d);
     if (rc) return rc;
     const int64_t N = d->num_steps * d->num_parallel, M = N * d->num_agents;
     int64_t rows, nb;
     actor_grid(M, rows, nb);
-    const int64_t actor = nb * actor_stride(d->obs_dim);
+    const int64_t actor = nb * (actor_stride(d->obs_dim) + (diag ? kDiagSums : 0));
     const int AD = d->num_agents * d->obs_dim;
     const CriticTiling ct = critic_tiling(AD, d->hidden_size);
     critic_grid(N, AD, d->hidden_size, ct, rows, nb);
@@ -1004,6 +1116,15 @@ extern "C" int64_t marlnav_ppo_work_size(const MarlnavPpoDims *d)
         critic += fb * (2 * d->hidden_size + 2) + (N * dh_pitch(d->hidden_size) + 1) / 2;
     }
     return actor > critic ? actor : critic;
+}
+
+}  // namespace
+
+extern "C" int64_t marlnav_ppo_work_size(const MarlnavPpoDims *d) { return work_size(d, false); }
+
+extern "C" int64_t marlnav_ppo_diag_work_size(const MarlnavPpoDims *d)
+{
+    return work_size(d, true);
 }
 
 namespace {
@@ -1068,7 +1189,7 @@ int check_critic_bufs(const MarlnavPpoBuffers *b)
 // marlnav_ppo_actor_grad; given: the same two with the Adam step folded in.
 int enqueue_actor(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
                   double ent_const, int advantage_mode, const AdvArgs *adv, const FoldArgs *fold,
-                  hipStream_t s, const ClipFoldArgs *clip = nullptr)
+                  hipStream_t s, const ClipFoldArgs *clip = nullptr, const DiagArgs *dg = nullptr)
 {
     PpoArgs a = make_args(d, b);
     actor_grid(a.M, a.rows_per_block, a.nblocks);
@@ -1083,7 +1204,14 @@ int enqueue_actor(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double ep
     const dim3 grid((unsigned)a.nblocks), blk(kThreads);
     const size_t lds = actor_lds_bytes(a.D);
     const bool env = advantage_mode == MARLNAV_ADVANTAGE_ENV;
-    if (clip) {  // the clipped update folded in (fold is NULL)
+    if (dg) {  // the diagnostic variant (adv, fold, clip are NULL)
+        const size_t dg_lds = fin_lds + sizeof(double) * kWaves;
+        if (env)
+            hipLaunchKernelGGL((actor_pass<kPairEnv>), grid, blk, lds, s, a, *dg);
+        else
+            hipLaunchKernelGGL((actor_pass<kPairReference>), grid, blk, lds, s, a, *dg);
+        hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), dg_lds, s, a, *dg);
+    } else if (clip) {  // the clipped update folded in (fold is NULL)
         if (env)
             hipLaunchKernelGGL((actor_pass<kPairEnv>), grid, blk, lds, s, a, *adv);
         else
@@ -1179,6 +1307,36 @@ extern "C" int marlnav_ppo_actor_grad_mode(const MarlnavPpoDims *d, const Marlna
     if (rc) return rc;
     return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
                          (hipStream_t)stream);
+}
+
+extern "C" int marlnav_ppo_actor_grad_diag(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                                           double epsilon, double ent_const, int advantage_mode,
+                                           double *diag, void *stream)
+{
+    int rc = check_dims(d);
+    if (rc) return rc;
+    rc = check_mode(advantage_mode);
+    if (rc) return rc;
+    rc = check_actor_bufs(b, advantage_mode);
+    if (rc) return rc;
+    if (!diag) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: diag is NULL");
+    if (reinterpret_cast<uintptr_t>(diag) & 7u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: diag must be 8-byte aligned");
+    const DiagArgs dg = {diag, nullptr, __builtin_inf(), 0, 1};
+    return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
+                         (hipStream_t)stream, nullptr, &dg);
+}
+
+// Update k of marlnav_ppo_train_phase_monitored (marlnav_adam.hip, which has
+// checked every argument): the diagnostic gradient launches, which write
+// diag_row and loss, decide the stop and, behind it, do nothing.
+__attribute__((visibility("hidden"))) int marlnav_internal_ppo_actor_diag(
+    const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon, double ent_const,
+    int advantage_mode, double *diag_row, int64_t *stop, double target_kl, int64_t k, void *stream)
+{
+    const DiagArgs dg = {diag_row, stop, target_kl, k, k == 0 ? 1 : 0};
+    return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
+                         (hipStream_t)stream, nullptr, &dg);
 }
 
 extern "C" int marlnav_ppo_actor_grad(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,

@@ -610,6 +610,7 @@ class FusedPPO(object):
         self._dims = abi.MarlnavPpoDims(num_agents=A, obs_dim=D, hidden_size=H)
         self._bufs = abi.MarlnavPpoBuffers()
         self._work = None
+        self.last_diag = self.last_stop = None     # of the last monitored train_phase
         for f, t in self._params:
             if t.grad is None:
                 t.grad = torch.zeros_like(t)
@@ -625,11 +626,11 @@ class FusedPPO(object):
             raise RuntimeError("the rollout buffer has no returns yet: call "
                                "buffer.process_rewards(gamma) (or collect()) before training")
 
-    def _bind(self, buffer, lo, hi, network='actor'):
+    def _bind(self, buffer, lo, hi, network='actor', diag=False):
         """Point the call's structs at steps lo..hi of the buffer; -> loss.
         The ``returns`` pointer: the normalised returns, or in the GAE mode
         the advantages (``network='actor'``) / the value targets
-        (``'critic'``)."""
+        (``'critic'``). ``diag``: the workspace of the diagnostic variant."""
         self._require(buffer)
         if self.advantage == 'gae':
             target = buffer.advantages if network == 'actor' else buffer.value_targets
@@ -663,7 +664,8 @@ class FusedPPO(object):
             setattr(b, f, t.data_ptr())
             setattr(b, "grad_" + f, g.data_ptr())
         d.num_parallel, d.num_steps = P, T
-        need = int(self._lib.marlnav_ppo_work_size(ctypes.byref(d)))
+        size = self._lib.marlnav_ppo_diag_work_size if diag else self._lib.marlnav_ppo_work_size
+        need = int(size(ctypes.byref(d)))
         if need < 0:
             abi.check(need, self._lib)
         if self._work is None or self._work.numel() < need:
@@ -673,15 +675,33 @@ class FusedPPO(object):
         b.loss = loss.data_ptr()
         return loss
 
-    def actor_loss_grad(self, buffer, lo, hi):
+    def actor_loss_grad(self, buffer, lo, hi, diag_out=None):
         """Actor loss (0-d float64 device tensor) of steps ``lo..hi`` of
         ``buffer``; the six actor parameters' ``.grad`` are overwritten. Two
-        launches on the current stream, no synchronisation."""
+        launches on the current stream, no synchronisation.
+
+        ``diag_out`` (None: the above): a contiguous float64 device tensor of
+        5 elements that receives the update's diagnostics (DESIGN.md §17,
+        ``marlnav_ppo_actor_grad_diag``): the surrogate mean, the entropy
+        mean, the approximate KL divergence from the rollout policy (the k3
+        estimator, mean of ``(ratio - 1) - log ratio``), the fraction of rows
+        whose ratio left ``[1 - epsilon, 1 + epsilon]`` and a status that is
+        0 here. Loss and ``.grad`` carry the bits they carry without it. Also
+        bound as ``actor_grad``."""
+        if diag_out is not None:
+            check_diag_out(diag_out, self.device)
+            loss = self._bind(buffer, lo, hi, diag=True)
+            abi.check(self._lib.marlnav_ppo_actor_grad_diag(
+                ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon, self.ent_const,
+                self._mode, diag_out.data_ptr(), _stream(self.device)), self._lib)
+            return loss
         loss = self._bind(buffer, lo, hi)
         abi.check(self._lib.marlnav_ppo_actor_grad_mode(
             ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon, self.ent_const,
             self._mode, _stream(self.device)), self._lib)
         return loss
+
+    actor_grad = actor_loss_grad
 
     def critic_loss_grad(self, buffer, lo, hi):
         """Critic loss (0-d float64 device tensor) of steps ``lo..hi``; the
@@ -985,6 +1005,24 @@ def check_max_grad_norm(max_grad_norm):
     if not g > 0.0:
         raise ValueError(f"max_grad_norm={max_grad_norm} must be > 0 (inf: record the norm only)")
     return g
+
+
+def check_target_kl(target_kl):
+    """``target_kl`` as a float; ValueError unless it is > 0 (``inf``
+    monitors only), as ``marlnav_ppo_train_phase_monitored`` demands."""
+    k = float(target_kl)
+    if not k > 0.0:     # a NaN is not greater
+        raise ValueError(f"target_kl={target_kl!r} must be > 0 (inf: monitor only)")
+    return k
+
+
+def check_diag_out(diag_out, device, rows=1, what="diag_out"):
+    """ValueError unless ``diag_out`` is a contiguous float64 tensor of
+    ``rows`` x 5 elements on ``device``."""
+    n = rows * abi.DIAG_ROW
+    if (not torch.is_tensor(diag_out) or diag_out.dtype != _F64 or diag_out.device != device
+            or diag_out.numel() != n or not diag_out.is_contiguous()):
+        raise ValueError(f"{what}: need a contiguous float64 tensor of {n} elements on {device}")
 
 
 def _train(ppo, loss_grad, update, network, buffer, optimizer, num_epochs, batch_size, log,

@@ -94,7 +94,12 @@ def stats_paths(out_dir, stamp):
             'cri_log': os.path.join(l, stamp + '_cri_loss.csv'),
             'epi_log': os.path.join(l, stamp + '_epi_stats.csv'),
             'act_gnorm_log': os.path.join(l, stamp + '_act_gnorm.csv'),
-            'cri_gnorm_log': os.path.join(l, stamp + '_cri_gnorm.csv')}
+            'cri_gnorm_log': os.path.join(l, stamp + '_cri_gnorm.csv'),
+            'act_kl_log': os.path.join(l, stamp + '_act_kl.csv'),
+            'act_clipfrac_log': os.path.join(l, stamp + '_act_clipfrac.csv'),
+            'act_entropy_log': os.path.join(l, stamp + '_act_entropy.csv'),
+            'act_stop_log': os.path.join(l, stamp + '_act_stop.csv'),
+            'act_kl_plot': os.path.join(p, stamp + '_act_kl.png')}
 
 
 def write_stats(logs, full_params, out_dir, stamp, plot=True):
@@ -106,7 +111,14 @@ def write_stats(logs, full_params, out_dir, stamp, plot=True):
     ``logs`` has ``actor_grad_norm`` / ``critic_grad_norm`` (a run with
     ``max_grad_norm``) also ``_act_gnorm.csv`` /
     ``_cri_gnorm.csv``, one-column like the losses; a ``logs`` without them
-    writes exactly the reference's files. Returns the paths written."""
+    writes exactly the reference's files. Where ``logs`` has the actor's
+    diagnostics (``actor_approx_kl`` ..., a run with ``target_kl`` or
+    ``log_diagnostics``) also ``_act_kl.csv``,
+    ``_act_clipfrac.csv``, ``_act_entropy.csv`` (one-column, one row per
+    update), ``_act_stop.csv`` (header ``Stopped at``, one row per rollout, -1
+    where the phase ran to its end) and with ``plot`` the figure
+    ``_act_kl.png``; the NaN of an update behind a stop is written as it is.
+    Returns the paths written."""
     paths = stats_paths(out_dir, stamp)
     os.makedirs(os.path.dirname(paths['params']), exist_ok=True)
     with open(paths['params'], 'w') as f:
@@ -129,6 +141,17 @@ def write_stats(logs, full_params, out_dir, stamp, plot=True):
             with open(paths[name], 'w', newline='') as f:
                 writer = csv.writer(f)
                 writer.writerow(['Value'])
+                writer.writerows([[num] for num in logs[key]])
+            written.append(paths[name])
+    diag = 'actor_approx_kl' in logs
+    if diag:
+        for key, name, head in (('actor_approx_kl', 'act_kl_log', 'Value'),
+                                ('actor_clip_frac', 'act_clipfrac_log', 'Value'),
+                                ('actor_entropy', 'act_entropy_log', 'Value'),
+                                ('actor_stopped_at', 'act_stop_log', 'Stopped at')):
+            with open(paths[name], 'w', newline='') as f:
+                writer = csv.writer(f)
+                writer.writerow([head])
                 writer.writerows([[num] for num in logs[key]])
             written.append(paths[name])
     if not plot:
@@ -155,11 +178,20 @@ def write_stats(logs, full_params, out_dir, stamp, plot=True):
     fig.suptitle('Episode endings')
     fig.savefig(paths['epi_plot'])
     plt.close(fig)
-    return written + [paths[k] for k in ('rew_plot', 'act_plot', 'cri_plot', 'epi_plot')]
+    written += [paths[k] for k in ('rew_plot', 'act_plot', 'cri_plot', 'epi_plot')]
+    if diag:
+        fig, ax = plt.subplots(1, 1)
+        ax.set(xlabel='batch_num', ylabel='value')
+        ax.plot(logs['actor_approx_kl'])
+        fig.suptitle('Actor approximate KL')
+        fig.savefig(paths['act_kl_plot'])
+        plt.close(fig)
+        written.append(paths['act_kl_plot'])
+    return written
 
 
 def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None, max_grad_norm=None,
-                norm_out=None):
+                norm_out=None, target_kl=None, diag_out=None, stop_out=None):
     """One whole ``train_actor`` (``network='actor'``) or ``train_critic``
     (``'critic'``) of the reference (models.py:160-198) over ``buffer`` as ONE
     C call, libmarlnav.so ``marlnav_ppo_train_phase``: ``num_epochs`` times
@@ -182,11 +214,37 @@ def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None, ma
     launches, the norm formed inside the finish launch) and stores the bits of
     ``ppo.actor_update(..., max_grad_norm=...)`` / ``critic_update``.
     ``norm_out``: None or a contiguous float64 device tensor like ``out`` for
-    the norms before clipping, in update order."""
+    the norms before clipping, in update order.
+
+    ``target_kl`` / ``diag_out`` (both None: the above, bit for bit), the
+    actor only (one ``marlnav_ppo_train_phase_monitored``):
+    every update writes a row of 5 doubles, ``[surrogate mean, entropy mean,
+    approximate KL, clip fraction, status]``, to ``diag_out`` (a contiguous
+    float64 device tensor of ``num_epochs * len(bounds)`` rows, allocated
+    where None) and the first update whose approximate KL exceeds
+    ``target_kl`` (or is NaN) abandons the phase on the device: that update
+    (status 1) stores its loss, row and ``.grad`` and takes no Adam step, the
+    updates behind it (status 2) cost their launches only and log NaN.
+    ``stop_out``: a contiguous int64 device tensor of 2 elements (allocated
+    where None) that receives ``[flag, stopped_at]``, reset by the call's
+    first launch; ``stopped_at`` is -1 where the phase ran to its end. The
+    comparison is with ``target_kl`` itself: for Stable-Baselines3's rule pass
+    1.5 times its value. ``diag_out`` alone monitors only (``target_kl =
+    inf``): no update stops, and losses, ``.grad``, parameters, moments and
+    the count carry the bits of the unmonitored call. Composes with
+    ``max_grad_norm`` and both advantage modes. The rows and the cell are kept
+    as ``ppo.last_diag`` / ``ppo.last_stop``. ``network='critic'`` with any of
+    the three is a ValueError."""
     nets = {'actor': abi.NETWORK_ACTOR, 'critic': abi.NETWORK_CRITIC,
             abi.NETWORK_ACTOR: abi.NETWORK_ACTOR, abi.NETWORK_CRITIC: abi.NETWORK_CRITIC}
     if network not in nets:
         raise ValueError(f"network must be 'actor' or 'critic', got {network!r}")
+    monitored = target_kl is not None or diag_out is not None or stop_out is not None
+    if monitored:
+        if nets[network] != abi.NETWORK_ACTOR:
+            raise ValueError("target_kl / diag_out / stop_out monitor the actor phase: "
+                             "network='critic' has no diagnostics")
+        target_kl = float('inf') if target_kl is None else rollout.check_target_kl(target_kl)
     ppo._require(buffer)
     lib, dev = ppo._lib, ppo.device
     bounds = minibatch_bounds(len(buffer), batch_size)
@@ -201,17 +259,42 @@ def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None, ma
     if (out.dtype != _F64 or out.device != dev or out.numel() != E * B
             or not out.is_contiguous()):
         raise ValueError(f"out: need a contiguous float64 tensor of {E * B} elements on {dev}")
+    if monitored:
+        if diag_out is None:
+            diag_out = torch.empty(E * B, abi.DIAG_ROW, dtype=_F64, device=dev)
+        rollout.check_diag_out(diag_out, dev, rows=E * B)
+        if stop_out is None:
+            stop_out = torch.empty(2, dtype=torch.int64, device=dev)
+        if (not torch.is_tensor(stop_out) or stop_out.dtype != torch.int64
+                or stop_out.device != dev or stop_out.numel() != 2
+                or not stop_out.is_contiguous()):
+            raise ValueError(f"stop_out: need a contiguous int64 tensor of 2 elements on {dev}")
     arr = (ctypes.c_int64 * (2 * B))(*[x for b in bounds for x in b])
     # step 0 of the storage, dims of the whole buffer
     ppo._bind(buffer, 0, len(buffer), 'actor' if nets[network] == abi.NETWORK_ACTOR else 'critic')
     d, b = ppo._dims, ppo._bufs
-    need = int(lib.marlnav_ppo_train_work_size(ctypes.byref(d), arr, B))
+    size = lib.marlnav_ppo_train_diag_work_size if monitored else lib.marlnav_ppo_train_work_size
+    need = int(size(ctypes.byref(d), arr, B))
     if need < 0:
         abi.check(need, lib)
     if ppo._work.numel() < need:
         ppo._work = torch.empty(need, dtype=_F64, device=dev)
     b.work = ppo._work.data_ptr()
     ad, ab = adam._bind()
+    if monitored:
+        if max_grad_norm is None:
+            if norm_out is not None:
+                raise ValueError("norm_out needs max_grad_norm (inf records the norms only)")
+            g, work, norms = abi.MAX_NORM_NONE, None, None
+        else:
+            g, work, norms = adam._clip_args(max_grad_norm, norm_out, count=E * B)
+        abi.check(lib.marlnav_ppo_train_phase_monitored(
+            nets[network], ctypes.byref(d), ctypes.byref(b), arr, B, E, ppo.epsilon,
+            ppo.ent_const, ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(), ppo._mode, g, work,
+            norms, target_kl, diag_out.data_ptr(), stop_out.data_ptr(),
+            torch._C._cuda_getCurrentRawStream(dev.index)), lib)
+        ppo.last_diag, ppo.last_stop = diag_out, stop_out
+        return out
     if max_grad_norm is None:
         if norm_out is not None:
             raise ValueError("norm_out needs max_grad_norm (inf records the norms only)")
@@ -252,6 +335,19 @@ class MAPPO(object):
     update's norm before clipping and ``logs()`` gains ``actor_grad_norm`` /
     ``critic_grad_norm``. A value that is not > 0 is a ValueError.
 
+    ``params['target_kl']`` (absent or None: today's behaviour) abandons the
+    remaining actor updates of a rollout once an update's approximate KL
+    divergence from the rollout policy exceeds it (decided on
+    the device, ``repeat()`` still does not synchronise); the comparison is
+    with the value itself, so pass 1.5 times Stable-Baselines3's ``target_kl``
+    for its rule. A value that is not > 0 is a ValueError.
+    ``params['log_diagnostics']`` (a bool) records the diagnostics without a
+    stop. With either, ``logs()`` gains ``actor_approx_kl``,
+    ``actor_clip_frac``, ``actor_entropy``, ``actor_surrogate`` and
+    ``actor_status`` (one per update, laid out as the losses) and
+    ``actor_stopped_at`` (one int per rollout, -1 where the phase ran to its
+    end); the loss of an update behind a stop is NaN.
+
     ``seed`` keys the policy kernel's normals (``FusedPolicy``); the modules'
     initial weights come from torch's global generator, as the reference's do.
 
@@ -278,6 +374,11 @@ class MAPPO(object):
         self.max_grad_norm = params.get('max_grad_norm')
         if self.max_grad_norm is not None:
             self.max_grad_norm = rollout.check_max_grad_norm(self.max_grad_norm)
+        self.target_kl = params.get('target_kl')
+        if self.target_kl is not None:
+            self.target_kl = rollout.check_target_kl(self.target_kl)
+        self.log_diagnostics = bool(params.get('log_diagnostics'))
+        self._monitored = self.target_kl is not None or self.log_diagnostics
         if env._rng != 'native' or env._init_sampler is not env._default_init_sampler:
             raise RuntimeError(f"{who} needs an env in native-RNG mode with its default init "
                                "sampler: a reference-RNG or user-assigned sampler is called on "
@@ -350,6 +451,7 @@ class MAPPO(object):
         self._cap = 0
         self._mean_log = self._epi_log = self._actor_log = self._critic_log = None
         self._actor_norm_log = self._critic_norm_log = None    # with max_grad_norm only
+        self._diag_log = self._stop_log = None    # with target_kl / log_diagnostics only
         self._reserve(max(1, int(total) // (self.buffer_len * self.num_parallel)) if total else 1)
         self._logs = _empty_logs()
 
@@ -370,12 +472,19 @@ class MAPPO(object):
             new += (torch.zeros(cap, U, dtype=_F64, device=self.device),
                     torch.zeros(cap, U, dtype=_F64, device=self.device))
             old += (self._actor_norm_log, self._critic_norm_log)
+        if self._monitored:
+            new += (torch.zeros(cap, U, abi.DIAG_ROW, dtype=_F64, device=self.device),
+                    torch.zeros(cap, 2, dtype=torch.int64, device=self.device))
+            new[-1][:, 1] = -1      # a rollout that was not trained on never stopped
+            old += (self._diag_log, self._stop_log)
         if self._cap:
             for n, o in zip(new, old):
                 n[:self._cap].copy_(o)
         self._mean_log, self._epi_log, self._actor_log, self._critic_log = new[:4]
         if self.max_grad_norm is not None:
-            self._actor_norm_log, self._critic_norm_log = new[4:]
+            self._actor_norm_log, self._critic_norm_log = new[4:6]
+        if self._monitored:
+            self._diag_log, self._stop_log = new[-2:]
         self._cap = cap
 
     def logs(self):
@@ -385,7 +494,12 @@ class MAPPO(object):
         rollout), ``actor`` / ``critic`` (one loss per update, in order; a
         rollout that was not trained on contributes zeros); with
         ``max_grad_norm`` also ``actor_grad_norm`` / ``critic_grad_norm``, each
-        update's gradient norm before clipping, laid out as the losses.
+        update's gradient norm before clipping, laid out as the losses; with
+        ``target_kl`` / ``log_diagnostics`` also ``actor_surrogate``,
+        ``actor_entropy``, ``actor_approx_kl``, ``actor_clip_frac`` and
+        ``actor_status`` (0 applied, 1 the update that raised the stop, 2
+        behind it), laid out as the losses, and ``actor_stopped_at``, one int
+        per rollout (-1: the phase ran to its end).
         Synchronises once:
         the device logs travel as one float64 tensor (the counters are exact
         below 2^53). Also kept as ``self._logs``."""
@@ -394,11 +508,15 @@ class MAPPO(object):
         clip = self.max_grad_norm is not None
         norms = [self._actor_norm_log[:r].flatten(),
                  self._critic_norm_log[:r].flatten()] if clip else []
+        mon = self._monitored
+        diag = [self._diag_log[:r].flatten(), self._stop_log[:r].to(_F64).flatten()] if mon else []
         flat = torch.cat([self._mean_log[:r], self._epi_log[:r].to(_F64).flatten(),
                           self._actor_log[:r].flatten(), self._critic_log[:r].flatten(),
-                          self._save_state.to(_F64)] + norms).cpu()
-        mean, epi, act, cri, save, *norms = torch.split(
-            flat, [r, 3 * r, r * U, r * U, 2] + [r * U] * len(norms))
+                          self._save_state.to(_F64)] + norms + diag).cpu()
+        mean, epi, act, cri, save, *rest = torch.split(
+            flat, [r, 3 * r, r * U, r * U, 2] + [r * U] * len(norms)
+            + ([r * U * abi.DIAG_ROW, 2 * r] if mon else []))
+        norms = rest[:len(norms)]
         epi = epi.view(r, 3).to(torch.int64).tolist()
         self._saves = (int(save[0]), int(save[1]))
         self._logs = {'epi_stats': {'trunc': [e[0] for e in epi], 'col': [e[1] for e in epi],
@@ -407,6 +525,13 @@ class MAPPO(object):
         if clip:
             self._logs['actor_grad_norm'] = norms[0].tolist()
             self._logs['critic_grad_norm'] = norms[1].tolist()
+        if mon:
+            rows = rest[-2].view(r * U, abi.DIAG_ROW)
+            for i, key in enumerate(('actor_surrogate', 'actor_entropy', 'actor_approx_kl',
+                                     'actor_clip_frac')):
+                self._logs[key] = rows[:, i].tolist()
+            self._logs['actor_status'] = [int(x) for x in rows[:, 4].tolist()]
+            self._logs['actor_stopped_at'] = [int(x) for x in rest[-1].view(r, 2)[:, 1].tolist()]
         return self._logs
 
     def save_count(self):
@@ -445,9 +570,14 @@ class MAPPO(object):
     def _phase(self, network, adam, log, norm_log):
         if self._r < 1:
             raise RuntimeError("no rollout to train on yet: call get_data() first")
+        r = self._r - 1
+        monitor = {}
+        if self._monitored and network == abi.NETWORK_ACTOR:
+            monitor = dict(target_kl=self.target_kl, diag_out=self._diag_log[r],
+                           stop_out=self._stop_log[r])
         train_phase(self.ppo, self.buffer, adam, network, self.num_epochs, self.batch_size,
-                    out=log[self._r - 1], max_grad_norm=self.max_grad_norm,
-                    norm_out=None if norm_log is None else norm_log[self._r - 1])
+                    out=log[r], max_grad_norm=self.max_grad_norm,
+                    norm_out=None if norm_log is None else norm_log[r], **monitor)
 
     def train_actor(self):
         """models.py:160-178 for the last rollout as ONE C call

@@ -179,6 +179,13 @@ def set_model_params(args, device):
         if not float(args.max_grad_norm) > 0.0:
             raise ValueError(f"max_grad_norm={args.max_grad_norm} must be > 0.")
         extra['max_grad_norm'] = args.max_grad_norm
+    # marlnav_amd only: the actor's target-KL stop and diagnostics, present only when asked for
+    if getattr(args, 'target_kl', None) is not None:
+        if not float(args.target_kl) > 0.0:
+            raise ValueError(f"target_kl={args.target_kl} must be > 0.")
+        extra['target_kl'] = args.target_kl
+    if getattr(args, 'log_diagnostics', False):
+        extra['log_diagnostics'] = True
     return {
         'actor': {'input_size': obs_size, 'hidden_size': args.hidden_size},
         'critic': {'input_size': obs_size * args.num_agents, 'hidden_size': args.hidden_size},
