@@ -798,6 +798,81 @@ int marlnav_ppo_train_phase_monitored(int network, const MarlnavPpoDims *dims,
                                       double *norm_log, double target_kl, double *diag_log,
                                       int64_t *stop, void *stream);
 
+/* Shuffled minibatches: the gradient launches over a list of
+ * steps, an on-device permutation generator, and a training phase that draws
+ * a fresh permutation of all stored steps per epoch. Additions only; the
+ * calls above and their kernels are untouched.
+ *
+ * marlnav_ppo_actor_grad_steps / marlnav_ppo_critic_grad_steps: the gradient
+ * calls above over the minibatch whose logical step slot s is step steps[s] of
+ * the storage.
+ *   dims->num_steps  T, the steps of the minibatch (the table's entries)
+ *   bufs             obs, actions, log_probs, values and returns address step 0
+ *                    of the storage; everything else as for the plain calls
+ *   steps            device, T int32, 4-byte aligned. Every entry must lie in
+ *                    [0, stored steps): the library cannot check a device table
+ *                    without a synchronisation and does not. Duplicates are fine
+ *   diag             NULL, or as for marlnav_ppo_actor_grad_diag (`work` then has
+ *                    marlnav_ppo_diag_work_size(dims) doubles)
+ * Logical row (slot, p, a) is the agent row of step steps[slot]; the means,
+ * both pairings, the tiles and every reduction order are those of the plain
+ * call over the logical order. So the call stores, bit for bit, what the plain
+ * call stores on a storage gathered with index_select(0, steps).
+ *
+ * marlnav_minibatch_permutations: one launch that writes E permutations of
+ * [0, L) into table (device, E x L int32), 1 <= L <= 65535, 1 <= E <= 65535.
+ *   seed     enters through its splitmix64 finalisation m, as the step's seed
+ *   network  MARLNAV_NETWORK_*: the two networks draw different permutations
+ *   counter  device, one uint64, 8-byte aligned: the call counter c. Every
+ *            thread reads it; behind a block barrier one thread stores c + 1. A
+ *            captured graph therefore draws new permutations at every replay
+ * Row e is a Fisher-Yates over the identity: for i = L - 1 down to 1, draw
+ * number n = L - 1 - i is word n & 1 of Philox2x32-10 with the counter words
+ * (e << 16 | n >> 1, lo32(c)) under the key
+ *   (uint32)m ^ fmix32((0x5045524D + network) * 0x9E3779B1 + hi32(c) * 0x85EBCA77
+ *                      + hi32(m))
+ * (fmix32: murmur3's finaliser), j = (uint64)word * (i + 1) >> 32, and row[i],
+ * row[j] are swapped. The multiply-shift is biased by at most L / 2^32 per
+ * draw (1.6e-5 at L = 65535, which is why a longer buffer is refused).
+ * tests/shuffle_ref.py restates it.
+ *
+ * marlnav_ppo_train_phase_shuffled: one train_actor / train_critic with fresh
+ * minibatches per epoch. dims and bufs describe the whole buffer of L =
+ * dims->num_steps stored steps. Epoch e uses row e of the table; minibatch j <
+ * L / batch_size of it is entries [j batch_size, (j + 1) batch_size), the last
+ * one extended by the L % batch_size left over: every stored step is used
+ * exactly once per epoch. num_epochs * (L / batch_size) updates, logged as by
+ * the other phase calls.
+ *   max_norm, norm_work, norm_log   as for _monitored (MARLNAV_MAX_NORM_NONE: off)
+ *   target_kl, diag_log, stop       0, NULL, NULL: off, and the critic is
+ *                                   allowed; else as for _monitored (actor only)
+ *   seed, counter, table            as for marlnav_minibatch_permutations; table
+ *                                   has num_epochs x L entries and holds the
+ *                                   phase's permutations afterwards
+ *   work    marlnav_ppo_train_shuffled_work_size(dims, batch_size, diag != 0)
+ * Every check is made before the first launch; then the permutation launch
+ * and the updates are enqueued. An update is the gather gradient launches and
+ * marlnav_adam_step's launches (the clipped three with max_norm, the gated
+ * forms with the monitor): this phase has no folded finish variants. */
+int marlnav_ppo_actor_grad_steps(const MarlnavPpoDims *dims, const MarlnavPpoBuffers *bufs,
+                                 const int32_t *steps, double epsilon, double ent_const,
+                                 int advantage_mode, double *diag, void *stream);
+int marlnav_ppo_critic_grad_steps(const MarlnavPpoDims *dims, const MarlnavPpoBuffers *bufs,
+                                  const int32_t *steps, double epsilon, void *stream);
+int marlnav_minibatch_permutations(int64_t L, int64_t E, uint64_t seed, int network,
+                                   uint64_t *counter, int32_t *table, void *stream);
+int64_t marlnav_ppo_train_shuffled_work_size(const MarlnavPpoDims *dims, int64_t batch_size,
+                                             int diag);
+int marlnav_ppo_train_phase_shuffled(int network, const MarlnavPpoDims *dims,
+                                     const MarlnavPpoBuffers *bufs, int64_t batch_size,
+                                     int64_t num_epochs, double epsilon, double ent_const,
+                                     const MarlnavAdamDims *adam_dims,
+                                     const MarlnavAdamBuffers *adam_bufs, double *loss_log,
+                                     int advantage_mode, double max_norm, double *norm_work,
+                                     double *norm_log, double target_kl, double *diag_log,
+                                     int64_t *stop, uint64_t seed, uint64_t *counter,
+                                     int32_t *table, void *stream);
+
 /* The checkpoint rule of MAPPO.get_data (models.py:127-129) on the device: if
  * *mean_rew > *max_rew (fp64; a NaN mean is not greater), copy src[i] to
  * dst[i] (numel[i] fp32 elements, any 4-byte alignment, i < num_tensors <=

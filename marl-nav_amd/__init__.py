@@ -10,7 +10,8 @@ from . import abi, evaluation, rollout, shard, training
 from .environment import Env
 from .evaluation import EvalResult, FusedActor, evaluate
 from .rollout import (FusedAdam, FusedPolicy, FusedPPO, RolloutBuffer, collect, collect_fused,
-                      gae_advantages, minibatch_bounds, train_actor, train_critic)
+                      gae_advantages, minibatch_bounds, shuffled_minibatch_sizes, train_actor,
+                      train_critic)
 from .training import MAPPO, Actor, Critic
 from .utils import (ActionScaler, ConstantSampler, MockInitializer, MockSampler,
                     ObsNormalizer, Observations, TriangleIntitializer, action_sampler, default_args,
@@ -24,4 +25,4 @@ __all__ = ["Env", "Observations", "ObsNormalizer", "ActionScaler", "MockInitiali
            "abi", "rollout", "shard", "evaluation", "FusedPolicy", "RolloutBuffer", "collect",
            "collect_fused", "FusedPPO", "FusedAdam", "minibatch_bounds", "train_actor", "train_critic",
            "FusedActor", "EvalResult", "evaluate", "training", "MAPPO", "Actor", "Critic",
-           "set_model_params", "gae_advantages"]
+           "set_model_params", "gae_advantages", "shuffled_minibatch_sizes"]

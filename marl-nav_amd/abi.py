@@ -171,6 +171,7 @@ CRITIC_VALUES_REQUIRED = ("obs_norm",) + POLICY_WEIGHT_FIELDS[6:] + ("values",)
 SNAPSHOT_MAX_TENSORS = 10
 DIAG_ROW = 5            # surrogate mean, entropy mean, approximate KL, clip fraction, status
 MAX_NORM_NONE = 0.0     # marlnav_ppo_train_phase_monitored without a clip
+SHUFFLE_MAX_STEPS = 65535   # marlnav_minibatch_permutations: the longest buffer (and most epochs)
 
 EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_formation_obs",
            "marlnav_counter_slots", "marlnav_counters_total",
@@ -189,6 +190,9 @@ EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_for
            "marlnav_ppo_train_phase_clipped", "marlnav_debug_clip_fold",
            "marlnav_ppo_actor_grad_diag", "marlnav_ppo_train_phase_monitored",
            "marlnav_ppo_diag_work_size", "marlnav_ppo_train_diag_work_size",
+           "marlnav_ppo_actor_grad_steps", "marlnav_ppo_critic_grad_steps",
+           "marlnav_minibatch_permutations", "marlnav_ppo_train_shuffled_work_size",
+           "marlnav_ppo_train_phase_shuffled",
            "marlnav_last_error", "marlnav_abi_version",
            "marlnav_debug_force_family", "marlnav_debug_last_family",
            "marlnav_debug_acos_range", "marlnav_debug_fastdiv_check")
@@ -315,6 +319,24 @@ def _declare(lib):
                                                       adam_dims_p, adam_bufs_p, _P, c.c_int,
                                                       c.c_double, _P, _P, c.c_double, _P, _P, _P]
     lib.marlnav_ppo_train_phase_monitored.restype = c.c_int
+    # the shuffled forms: a device table of steps; the phase adds batch_size,
+    # seed, counter, table
+    lib.marlnav_ppo_actor_grad_steps.argtypes = [ppo_dims_p, ppo_bufs_p, _P, c.c_double,
+                                                 c.c_double, c.c_int, _P, _P]
+    lib.marlnav_ppo_actor_grad_steps.restype = c.c_int
+    lib.marlnav_ppo_critic_grad_steps.argtypes = [ppo_dims_p, ppo_bufs_p, _P, c.c_double, _P]
+    lib.marlnav_ppo_critic_grad_steps.restype = c.c_int
+    lib.marlnav_minibatch_permutations.argtypes = [c.c_int64, c.c_int64, c.c_uint64, c.c_int, _P,
+                                                   _P, _P]
+    lib.marlnav_minibatch_permutations.restype = c.c_int
+    lib.marlnav_ppo_train_shuffled_work_size.argtypes = [ppo_dims_p, c.c_int64, c.c_int]
+    lib.marlnav_ppo_train_shuffled_work_size.restype = c.c_int64
+    lib.marlnav_ppo_train_phase_shuffled.argtypes = [c.c_int, ppo_dims_p, ppo_bufs_p, c.c_int64,
+                                                     c.c_int64, c.c_double, c.c_double,
+                                                     adam_dims_p, adam_bufs_p, _P, c.c_int,
+                                                     c.c_double, _P, _P, c.c_double, _P, _P,
+                                                     c.c_uint64, _P, _P, _P]
+    lib.marlnav_ppo_train_phase_shuffled.restype = c.c_int
     lib.marlnav_debug_clip_fold.argtypes = [c.c_int]
     lib.marlnav_debug_clip_fold.restype = c.c_int
     lib.marlnav_last_error.argtypes = []

@@ -46,6 +46,14 @@ adds ``_act_kl.csv``, ``_act_clipfrac.csv``, ``_act_entropy.csv``,
 ``--gae-lambda`` and ``--max-grad-norm``.
 
     python -m marlnav_amd --train --target-kl 0.02 -np 4096 -bl 16 -bs 8 -ne 4 -nt 1048576
+
+``--shuffle-minibatches`` with ``--train`` draws a fresh random permutation of
+all ``buffer_len`` stored steps per epoch, on the device, and cuts the
+minibatches from it, the buffer's final step included; the
+default walks the reference's fixed contiguous slices. Keyed by ``-se``; it
+composes with every option above and is refused without ``--train``.
+
+    python -m marlnav_amd --train --shuffle-minibatches -np 4096 -bl 16 -bs 8 -ne 4 -nt 1048576
 """
 import argparse
 import sys
@@ -131,6 +139,10 @@ def build_parser():
     a('--log-diagnostics', action='store_true',
       help='with --train: log every actor update\'s approximate KL, clip fraction, entropy '
            'and surrogate')
+    a('--shuffle-minibatches', action='store_true',
+      help='with --train: a fresh random permutation of all stored steps per epoch, cut into '
+           'the minibatches (default: the reference\'s fixed contiguous slices, which never '
+           'train on the buffer\'s final step)')
     a('--out-dir', default='.', help='with --train: where weights/, logs/ and plots/ go')
     a('--plot-dir', default='plots', help='directory of the saved figures')
     a('--no-plots', action='store_true', help='skip the figures, print the series')
@@ -143,6 +155,9 @@ def main(argv=None):
     import torch
     pkg = importlib.import_module("marl-nav_amd")
     args = build_parser().parse_args(argv)
+    if args.shuffle_minibatches and not args.train:
+        print("--shuffle-minibatches is an option of --train (marlnav_amd.MAPPO)", file=sys.stderr)
+        return 2
     if args.evaluate:
         return _evaluate(pkg, args)
     if args.train:

@@ -64,6 +64,7 @@ __attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const 
 namespace {
 
 #include "host_util.h"
+#include "device_rng.h"  // Philox2x32-10 and the key mixing, for the minibatch permutations
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -850,6 +851,204 @@ extern "C" int marlnav_ppo_train_phase_monitored(
             if (rc) return rc;
             const ClipArgs ck = {max_norm, norm_work, norm_log ? norm_log + k : nullptr};
             rc = enqueue_adam(ad, ab, (hipStream_t)stream, clipped ? &ck : nullptr, stop);
+            if (rc) return rc;
+        }
+    return 0;
+}
+
+// =========================================================================
+// shuffled minibatches
+// =========================================================================
+__attribute__((visibility("hidden"))) int marlnav_internal_ppo_grad_steps(
+    int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, const int32_t *steps,
+    double epsilon, double ent_const, int advantage_mode, double *diag_row, int64_t *stop,
+    double target_kl, int64_t k, void *stream, int check_only);
+
+namespace {
+
+constexpr int64_t kPermMaxLen = 65535;     // L: a draw's block index stays below 2^15
+constexpr int64_t kPermMaxEpochs = 65535;  // E: the epoch fills the counter word's high half
+constexpr uint32_t kPermBlock = 0x5045524Du;  // "PERM": the key's block tag, + the network
+
+// E uniform permutations of [0, L) in one launch of one block: thread e (then
+// e + 256, ...) runs a Fisher-Yates over the identity in row e of the table.
+//   c        the 64-bit call counter, read from *counter by every thread
+//   key      native_key(m, kPermBlock + network, c), m = native_seed_mix(seed):
+//            (uint32)m ^ fmix32((kPermBlock + network) * 0x9E3779B1
+//                               + hi32(c) * 0x85EBCA77 + hi32(m))
+//   block b  of epoch e: Philox2x32-10 of the counter (e << 16 | b, lo32(c))
+//            under the key; b < 2^15 and e < 2^16, so no two (e, b) share a word
+//   draws    position i = L - 1 down to 1 takes draw number n = L - 1 - i: word
+//            n & 1 of block n >> 1; j = (uint64)word * (i + 1) >> 32 in [0, i];
+//            row[i] and row[j] are swapped
+// The multiply-shift picks each j with probability within 2^-32 of 1 / (i +
+// 1): a bias of at most (i + 1) / 2^32 <= L / 2^32 per draw, below 1.6e-5 at
+// the largest L = 65 535 the call accepts. Behind the block's barrier, when
+// every thread holds c, thread 0 stores c + 1: a replayed graph draws anew,
+// as the Adam step count advances. Plain vector loads and stores only, each
+// row read and written by its one thread; no atomics.
+__global__ void __launch_bounds__(kThreads) minibatch_permutations(int32_t *table, int L, int E,
+                                                                    uint64_t m, uint32_t network,
+                                                                    uint64_t *counter)
+{
+    const uint64_t c = *counter;
+    __syncthreads();
+    if (threadIdx.x == 0) *counter = c + 1;
+    const uint32_t key = native_key(m, kPermBlock + network, c);
+    for (int e = threadIdx.x; e < E; e += kThreads) {
+        int32_t *__restrict__ row = table + (int64_t)e * L;
+        for (int i = 0; i < L; ++i) row[i] = i;
+        uint32_t w0 = 0, w1 = 0;
+        for (int i = L - 1, n = 0; i >= 1; --i, ++n) {
+            if ((n & 1) == 0) {
+                w0 = ((uint32_t)e << 16) | (uint32_t)(n >> 1);
+                w1 = (uint32_t)c;
+                philox2x32_10(w0, w1, key);
+            }
+            const uint32_t word = (n & 1) ? w1 : w0;
+            const int j = (int)(((uint64_t)word * (uint32_t)(i + 1)) >> 32);
+            const int32_t a = row[i], bj = row[j];
+            row[i] = bj;
+            row[j] = a;
+        }
+    }
+}
+
+int check_permutations(int64_t L, int64_t E, int network, const void *counter, const void *table)
+{
+    if (L < 1 || L > kPermMaxLen)
+        return failf(MARLNAV_EINVAL, "shuffle: %lld steps outside [1, %lld]", (long long)L,
+                     (long long)kPermMaxLen);
+    if (E < 1 || E > kPermMaxEpochs)
+        return failf(MARLNAV_EINVAL, "shuffle: num_epochs=%lld outside [1, %lld]", (long long)E,
+                     (long long)kPermMaxEpochs);
+    if (network != MARLNAV_NETWORK_ACTOR && network != MARLNAV_NETWORK_CRITIC)
+        return failf(MARLNAV_EINVAL, "shuffle: network=%d must be MARLNAV_NETWORK_ACTOR or _CRITIC",
+                     network);
+    if (!counter) return marlnav_internal_fail(MARLNAV_EINVAL, "shuffle: counter is NULL");
+    if (addr(counter) & 7u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "shuffle: counter must be 8-byte aligned");
+    if (!table) return marlnav_internal_fail(MARLNAV_EINVAL, "shuffle: table is NULL");
+    if (addr(table) & 3u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "shuffle: table must be 4-byte aligned");
+    return 0;
+}
+
+void enqueue_permutations(int64_t L, int64_t E, uint64_t seed, int network, uint64_t *counter,
+                          int32_t *table, hipStream_t s)
+{
+    hipLaunchKernelGGL(minibatch_permutations, dim3(1), dim3(kThreads), 0, s, table, (int)L,
+                       (int)E, native_seed_mix(seed), (uint32_t)network, counter);
+}
+
+// minibatch j of an epoch: entries [j bs, (j + 1) bs) of its permutation, the
+// last one with the L % bs left over
+inline int64_t shuffled_steps(int64_t L, int64_t bs, int64_t j)
+{
+    return j + 1 < L / bs ? bs : L - j * bs;
+}
+
+}  // namespace
+
+extern "C" int marlnav_minibatch_permutations(int64_t L, int64_t E, uint64_t seed, int network,
+                                              uint64_t *counter, int32_t *table, void *stream)
+{
+    const int rc = check_permutations(L, E, network, counter, table);
+    if (rc) return rc;
+    enqueue_permutations(L, E, seed, network, counter, table, (hipStream_t)stream);
+    return launch_status();
+}
+
+extern "C" int64_t marlnav_ppo_train_shuffled_work_size(const MarlnavPpoDims *d,
+                                                        int64_t batch_size, int diag)
+{
+    if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
+    const int64_t L = d->num_steps;
+    if (batch_size < 1 || L / batch_size < 1)
+        return failf(MARLNAV_EINVAL, "shuffle: batch_size=%lld gives no minibatch of %lld steps",
+                     (long long)batch_size, (long long)L);
+    int64_t need = 0;
+    const int64_t B = L / batch_size;
+    for (int64_t j = B > 1 ? B - 2 : 0; j < B; ++j) {  // the two sizes an epoch has
+        MarlnavPpoDims md = *d;
+        md.num_steps = shuffled_steps(L, batch_size, j);
+        const int64_t w = diag ? marlnav_ppo_diag_work_size(&md) : marlnav_ppo_work_size(&md);
+        if (w < 0) return w;
+        if (w > need) need = w;
+    }
+    return need;
+}
+
+extern "C" int marlnav_ppo_train_phase_shuffled(
+    int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, int64_t batch_size,
+    int64_t num_epochs, double epsilon, double ent_const, const MarlnavAdamDims *ad,
+    const MarlnavAdamBuffers *ab, double *loss_log, int advantage_mode, double max_norm,
+    double *norm_work, double *norm_log, double target_kl, double *diag_log, int64_t *stop,
+    uint64_t seed, uint64_t *counter, int32_t *table, void *stream)
+{
+    // ---- every check before the first launch
+    const bool monitored = target_kl != 0.0 || diag_log || stop;
+    if (monitored && network == MARLNAV_NETWORK_CRITIC)
+        return marlnav_internal_fail(MARLNAV_EINVAL,
+                                     "train: target_kl / diag_log / stop monitor the actor; "
+                                     "network is MARLNAV_NETWORK_CRITIC");
+    const bool clipped = max_norm != MARLNAV_MAX_NORM_NONE;  // a NaN is refused by check_clip
+    if (!clipped && (norm_work || norm_log))
+        return marlnav_internal_fail(MARLNAV_EINVAL,
+                                     "clip: norm_work and norm_log must be NULL with "
+                                     "max_norm = MARLNAV_MAX_NORM_NONE");
+    if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
+    const int64_t L = d->num_steps;
+    if (batch_size < 1 || L / batch_size < 1)
+        return failf(MARLNAV_EINVAL, "shuffle: batch_size=%lld gives no minibatch of %lld steps",
+                     (long long)batch_size, (long long)L);
+    int rc = check_permutations(L, num_epochs, network, counter, table);
+    if (rc) return rc;
+    const int64_t B = L / batch_size;
+    // the contiguous phase's checks, over the whole buffer as one range
+    const int64_t whole[2] = {0, L};
+    const ClipArgs clip = {max_norm, norm_work, norm_log};
+    rc = check_train_phase(network, d, b, whole, 1, num_epochs, epsilon, ent_const, ad, ab,
+                           loss_log, advantage_mode, clipped ? &clip : nullptr, stream);
+    if (rc) return rc;
+    if (monitored) {
+        if (!(target_kl > 0.0))  // a NaN is not greater
+            return failf(MARLNAV_EINVAL, "train: target_kl=%g must be > 0 (+inf: monitor only)",
+                         target_kl);
+        if (!diag_log) return marlnav_internal_fail(MARLNAV_EINVAL, "train: diag_log is NULL");
+        if (addr(diag_log) & 7u)
+            return marlnav_internal_fail(MARLNAV_EINVAL, "train: diag_log must be 8-byte aligned");
+        if (!stop) return marlnav_internal_fail(MARLNAV_EINVAL, "train: stop is NULL");
+        if (addr(stop) & 7u)
+            return marlnav_internal_fail(MARLNAV_EINVAL, "train: stop must be 8-byte aligned");
+    }
+    MarlnavPpoDims md = *d;
+    MarlnavPpoBuffers mb = *b;
+    for (int64_t j = B > 1 ? B - 2 : 0; j < B; ++j) {  // dims of the two minibatch sizes
+        md.num_steps = shuffled_steps(L, batch_size, j);
+        rc = marlnav_internal_ppo_grad_steps(network, &md, &mb, table, epsilon, ent_const,
+                                             advantage_mode, nullptr, nullptr, 0.0, 0, stream, 1);
+        if (rc) return rc;
+    }
+    // ---- the permutations, then num_epochs x B updates, epoch-major: the gather
+    // gradient launches and the Adam launches (clipped and gated where asked).
+    // Nothing is folded: the finish kernels' folds have no gather variants.
+    enqueue_permutations(L, num_epochs, seed, network, counter, table, (hipStream_t)stream);
+    rc = launch_status();
+    if (rc) return rc;
+    int64_t k = 0;
+    for (int64_t e = 0; e < num_epochs; ++e)
+        for (int64_t j = 0; j < B; ++j, ++k) {
+            md.num_steps = shuffled_steps(L, batch_size, j);
+            mb.loss = loss_log + k;
+            rc = marlnav_internal_ppo_grad_steps(
+                network, &md, &mb, table + e * L + j * batch_size, epsilon, ent_const,
+                advantage_mode, monitored ? diag_log + MARLNAV_DIAG_ROW * k : nullptr, stop,
+                target_kl, k, stream, 0);
+            if (rc) return rc;
+            const ClipArgs ck = {max_norm, norm_work, norm_log ? norm_log + k : nullptr};
+            rc = enqueue_adam(ad, ab, (hipStream_t)stream, clipped ? &ck : nullptr,
+                              monitored ? stop : nullptr);
             if (rc) return rc;
         }
     return 0;

@@ -93,6 +93,70 @@ struct PpoArgs {
     float clip_lo, clip_hi, eps_f, ent_f;
 };
 
+// ---- the step gather (marlnav_ppo_*_grad_steps). A pass
+// kernel instantiated with GatherArgs reads logical step slot s of the
+// minibatch from physical step steps[s] of the storage, whose step 0 the data
+// pointers address. Only the addresses of obs, actions, log_probs, values and
+// returns change: the grid, the tiles, the workspace and every reduction order
+// stay functions of the logical row, so the stored bits are those of the
+// contiguous call on a storage gathered with index_select(0, steps). The
+// instantiations with PpoArgs are the kernels as they were.
+struct GatherArgs : PpoArgs {
+    const int32_t *steps;  // [T], every entry a stored step (not checked here)
+};
+
+template <class ARGS>
+struct is_gather {
+    static constexpr bool value = false;
+};
+template <>
+struct is_gather<GatherArgs> {
+    static constexpr bool value = true;
+};
+
+// The physical rows of one tile. R rows make a step (P A agent rows, or P env
+// rows); the tile starts at logical row `base` = slot0 R + off0, found with
+// the one wave-uniform division the contiguous kernels already pay per tile.
+// at(dlt), 0 <= dlt < TILE, is the physical row of logical row base + dlt.
+// R >= TILE: the tile meets at most one step boundary, so the two table
+// entries it can need are wave-uniform loads and a row costs an add, a compare
+// and a select. R < TILE: the tile spans several steps; off0 + dlt < 2 TILE
+// divides in 32 bits and the entry is a per-lane load from a table of a few
+// cache lines. No row divides in 64 bits.
+template <int TILE>
+struct StepWalk {
+    const int32_t *steps;
+    int64_t R, slot0, off0;
+    int64_t p0, p1;  // first physical row of the steps of slot0 and of slot0 + 1
+
+    __device__ __forceinline__ void start(const int32_t *__restrict__ st, int64_t T, int64_t R_,
+                                          int64_t base)
+    {
+        steps = st;
+        R = R_;
+        slot0 = base / R;
+        off0 = base - slot0 * R;
+        p0 = (int64_t)st[slot0] * R;
+        p1 = (int64_t)st[slot0 + 1 < T ? slot0 + 1 : slot0] * R;
+    }
+    // R >= TILE: rows [0, run0()) of the tile are consecutive from physical row
+    // first0(), the rest consecutive from first1() + dlt: a row loop split there
+    // keeps the contiguous kernel's constant stride in each half
+    __device__ __forceinline__ int64_t run0() const { return R - off0; }
+    __device__ __forceinline__ int64_t first0() const { return p0 + off0; }
+    __device__ __forceinline__ int64_t first1() const { return p1 + off0 - R; }
+    __device__ __forceinline__ int64_t at(int dlt) const
+    {
+        if (R >= TILE) {
+            const int64_t off = off0 + dlt;
+            return off < R ? p0 + off : p1 + (off - R);
+        }
+        const uint32_t r = (uint32_t)R, o = (uint32_t)off0 + (uint32_t)dlt;
+        const uint32_t q = o / r;
+        return (int64_t)steps[slot0 + q] * R + (o - q * r);
+    }
+};
+
 // ---- the Adam step folded into the finish kernels (marlnav_ppo_train_phase,
 // DESIGN.md §14). AdvArgs: what one thread of the pass launch needs to advance
 // the count and publish the step's scalars. FoldArgs: what the finish launch,
@@ -251,10 +315,11 @@ __device__ __host__ inline int64_t actor_stride(int D) { return 4 * (int64_t)(D 
 // env, read as a ready fp64 advantage; values is not read.
 enum { kPairReference = 0, kPairEnv = 1 };
 
-template <int PAIRING, class... X>
-__global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
+template <int PAIRING, class ARGS, class... X>
+__global__ void __launch_bounds__(kThreads) actor_pass(ARGS g, X... x)
 {
     constexpr bool kDiag = is_diag<X...>::value;
+    constexpr bool kGather = is_gather<ARGS>::value;
     if constexpr (kDiag) {
         // an update behind the stop costs its launches only (uniform per grid)
         const DiagArgs &dg = only(x...);
@@ -319,6 +384,10 @@ __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
     const int64_t row_lo = (int64_t)blockIdx.x * g.rows_per_block;
     const int64_t row_hi = row_lo + g.rows_per_block < M ? row_lo + g.rows_per_block : M;
     const double be0 = s_b[0], be1 = s_b[1], be2 = s_b[2], be3 = s_b[3];
+    // GATHER: the tile's agent rows (wk), the env rows its advantages pair with
+    // (wn) and, for the reference pairing's wrap past N, those from env row 0 (wz)
+    StepWalk<kActorTile> wk, wn, wz;
+    if constexpr (kGather && PAIRING == kPairReference) wz.start(g.steps, g.T, g.P, 0);
 
     for (int64_t tile = row_lo; tile < row_hi; tile += kActorTile) {
         // ---- phase 1: thread = row
@@ -326,9 +395,15 @@ __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
         // wave-uniform: one scalar division per tile
         const int64_t tile_n = PAIRING == kPairEnv ? tile / g.A : tile % N;
         const int tile_a = PAIRING == kPairEnv ? (int)(tile - tile_n * g.A) : 0;
+        if constexpr (kGather) {
+            wk.start(g.steps, g.T, g.P * g.A, tile);
+            wn.start(g.steps, g.T, g.P, tile_n);
+        }
         float4 gr4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (row < row_hi) {
-            const float *__restrict__ xr = g.b.obs + row * D;
+            int64_t prow = row;  // the row in the storage
+            if constexpr (kGather) prow = wk.at(t);
+            const float *__restrict__ xr = g.b.obs + prow * D;
             double a0 = be0, a1 = be1, a2 = be2, a3 = be3;
             for (int k = 0; k < D; ++k) {
                 const double2 wa = *reinterpret_cast<const double2 *>(s_w + 4 * k);
@@ -343,22 +418,28 @@ __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
             const float mu0 = tanhf(p0), mu1 = tanhf(p1);
             const float v0 = p2 > 20.0f ? p2 : log1pf(expf(p2));
             const float v1 = p3 > 20.0f ? p3 : log1pf(expf(p3));
-            const float d0 = g.b.actions[2 * row] - mu0, d1 = g.b.actions[2 * row + 1] - mu1;
+            const float d0 = g.b.actions[2 * prow] - mu0, d1 = g.b.actions[2 * prow + 1] - mu1;
             const float iv0 = 1.0f / v0, iv1 = 1.0f / v1;
             const float q0 = d0 * d0 * iv0, q1 = d1 * d1 * iv1;
             const float ld = logf(v0) + logf(v1);
             const float lp = __builtin_fmaf(-0.5f, q0 + q1, __builtin_fmaf(-0.5f, ld, -kLog2Pi));
             const float ent = __builtin_fmaf(0.5f, ld, 1.0f + kLog2Pi);
-            const float lr = lp - g.b.log_probs[row];
+            const float lr = lp - g.b.log_probs[prow];
             const float ratio = expf(lr);
             double adv;
             if constexpr (PAIRING == kPairEnv) {
                 // row / A: the row's own env row, tile = tile_n A + tile_a
-                adv = g.b.returns[tile_n + (tile_a + t) / g.A];
+                if constexpr (kGather)
+                    adv = g.b.returns[wn.at((tile_a + t) / g.A)];
+                else
+                    adv = g.b.returns[tile_n + (tile_a + t) / g.A];
             } else {
                 // row mod N: the reference's repeat(num_agents), not the row's env
                 int64_t n = tile_n + t;
-                if (n >= N) n = N >= kActorTile ? n - N : n % N;
+                const bool wrapped = n >= N;
+                if (wrapped) n = N >= kActorTile ? n - N : n % N;
+                // GATHER: a wrapped n lies below kActorTile, counted from env row 0
+                if constexpr (kGather) n = wrapped ? wz.at((int)n) : wn.at(t);
                 adv = g.b.returns[n] - (double)g.b.values[n];
             }
             const float rc = ratio < g.clip_lo ? g.clip_lo : (ratio > g.clip_hi ? g.clip_hi : ratio);
@@ -391,18 +472,49 @@ __global__ void __launch_bounds__(kThreads) actor_pass(PpoArgs g, X... x)
         if (own) {
             const int64_t left = row_hi - tile;
             const int nrows = left < kActorTile ? (int)left : kActorTile;
-            for (int r = us; r < nrows; r += slices) {
-                const float4 gv = *reinterpret_cast<const float4 *>(s_g + 4 * r);
-                const float *__restrict__ xr = g.b.obs + (tile + r) * D;
+            if constexpr (kGather) {
+                // row r of the tile at physical row `first` + r
+                auto add_row = [&](int r, int64_t first) {
+                    const float4 gv = *reinterpret_cast<const float4 *>(s_g + 4 * r);
+                    const float *__restrict__ xr = g.b.obs + (first + r) * D;
+    #pragma unroll
+                    for (int i = 0; i < kActorColsPerThread; ++i) {
+                        const int c = kk + i * kThreads;
+                        if (c < ncol) {
+                            const double xv = c < D ? (double)xr[c] : 1.0;
+                            acc[i][0] = __builtin_fma((double)gv.x, xv, acc[i][0]);
+                            acc[i][1] = __builtin_fma((double)gv.y, xv, acc[i][1]);
+                            acc[i][2] = __builtin_fma((double)gv.z, xv, acc[i][2]);
+                            acc[i][3] = __builtin_fma((double)gv.w, xv, acc[i][3]);
+                        }
+                    }
+                };
+                // the thread's rows in the same order, in two constant-stride
+                // runs where the tile meets at most one step boundary
+                int r = us;
+                if (wk.R >= kActorTile) {
+                    const int64_t run0 = wk.run0();
+                    const int n0 = run0 < nrows ? (int)run0 : nrows;
+                    const int64_t f0 = wk.first0(), f1 = wk.first1();
+                    for (; r < n0; r += slices) add_row(r, f0);
+                    for (; r < nrows; r += slices) add_row(r, f1);
+                } else {
+                    for (; r < nrows; r += slices) add_row(r, wk.at(r) - r);
+                }
+            } else {
+                for (int r = us; r < nrows; r += slices) {
+                    const float4 gv = *reinterpret_cast<const float4 *>(s_g + 4 * r);
+                    const float *__restrict__ xr = g.b.obs + (tile + r) * D;
 #pragma unroll
-                for (int i = 0; i < kActorColsPerThread; ++i) {
-                    const int c = kk + i * kThreads;
-                    if (c < ncol) {
-                        const double xv = c < D ? (double)xr[c] : 1.0;
-                        acc[i][0] = __builtin_fma((double)gv.x, xv, acc[i][0]);
-                        acc[i][1] = __builtin_fma((double)gv.y, xv, acc[i][1]);
-                        acc[i][2] = __builtin_fma((double)gv.z, xv, acc[i][2]);
-                        acc[i][3] = __builtin_fma((double)gv.w, xv, acc[i][3]);
+                    for (int i = 0; i < kActorColsPerThread; ++i) {
+                        const int c = kk + i * kThreads;
+                        if (c < ncol) {
+                            const double xv = c < D ? (double)xr[c] : 1.0;
+                            acc[i][0] = __builtin_fma((double)gv.x, xv, acc[i][0]);
+                            acc[i][1] = __builtin_fma((double)gv.y, xv, acc[i][1]);
+                            acc[i][2] = __builtin_fma((double)gv.z, xv, acc[i][2]);
+                            acc[i][3] = __builtin_fma((double)gv.w, xv, acc[i][3]);
+                        }
                     }
                 }
             }
@@ -731,10 +843,11 @@ constexpr size_t kCriticLdsBytes =
 // MODE kBackward: the outer product alone, dh read back from the workspace.
 enum { kFused = 0, kForward = 1, kBackward = 2 };
 
-template <int JT, int MODE, class... X>
-__global__ void __launch_bounds__(kThreads) critic_pass(PpoArgs g, CriticTiling ct, float *dhbuf,
+template <int JT, int MODE, class ARGS, class... X>
+__global__ void __launch_bounds__(kThreads) critic_pass(ARGS g, CriticTiling ct, float *dhbuf,
                                                          int hp, int vec4, X... x)
 {
+    constexpr bool kGather = is_gather<ARGS>::value;
     const int A = g.A, D = g.D, H = g.H;
     const int AD = A * D;
     extern __shared__ __attribute__((aligned(16))) float s_dyn[];
@@ -775,7 +888,9 @@ __global__ void __launch_bounds__(kThreads) critic_pass(PpoArgs g, CriticTiling 
     const int64_t row_lo = (int64_t)blockIdx.x * rows_blk;
     const int64_t row_hi = row_lo + rows_blk < N ? row_lo + rows_blk : N;
 
+    StepWalk<kCriticTile> wk;  // GATHER: the tile's env rows in the storage
     for (int64_t tile = row_lo; tile < row_hi; tile += kCriticTile) {
+        if constexpr (kGather) wk.start(g.steps, g.T, g.P, tile);
         if constexpr (MODE == kBackward) {
             // ---- dh of the tile's rows and the block's units, from the workspace
             for (int idx = t; idx < kCriticTile * ct.ub; idx += kThreads) {
@@ -791,7 +906,9 @@ __global__ void __launch_bounds__(kThreads) critic_pass(PpoArgs g, CriticTiling 
             {
                 const int64_t row_raw = tile + lane;
                 const int64_t row = row_raw < row_hi ? row_raw : row_hi - 1;  // stays in bounds
-                const float *__restrict__ xe = g.b.obs + row * AD;
+                int64_t prow = row;
+                if constexpr (kGather) prow = wk.at((int)(row - tile));
+                const float *__restrict__ xe = g.b.obs + prow * AD;
                 float part = 0.0f;
                 for (int j = j0; j < j1; j += 8) {
                     // fp32 FMA chains of kFwdChain inputs, added up in fp64:
@@ -854,8 +971,10 @@ __global__ void __launch_bounds__(kThreads) critic_pass(PpoArgs g, CriticTiling 
 #pragma unroll
                     for (int w = 1; w < kWaves; ++w) nv += s_part[w * kCriticTile + t];
                     nv += b2;
-                    const double ret = g.b.returns[row];
-                    const float val = g.b.values[row];
+                    int64_t prow = row;
+                    if constexpr (kGather) prow = wk.at(t);
+                    const double ret = g.b.returns[prow];
+                    const float val = g.b.values[prow];
                     const float lo = val - g.eps_f, hi = val + g.eps_f;
                     const float cl = nv < lo ? lo : (nv > hi ? hi : nv);
                     const double e0 = (double)nv - ret, e1 = (double)cl - ret;
@@ -900,19 +1019,54 @@ __global__ void __launch_bounds__(kThreads) critic_pass(PpoArgs g, CriticTiling 
         if (MODE != kForward && own) {
             const int64_t left = row_hi - tile;
             const int nrows = left < kCriticTile ? (int)left : kCriticTile;
-            const float *__restrict__ xc = g.b.obs + tile * AD + col;
-            for (int r = 0; r < nrows; ++r) {
-                const double xv = (double)xc[(int64_t)r * AD];
-                // uj0 is a multiple of JT >= 8 floats, the row pitch of 16 bytes
-                const float4 *__restrict__ dh =
-                    reinterpret_cast<const float4 *>(s_h + r * kHPad + uj0);
+            if constexpr (kGather) {
+                // rows [r0, r1) of the tile, row r at physical row `first` + r
+                auto add_rows = [&](int r0, int r1, int64_t first) {
+                    const float *__restrict__ xc = g.b.obs + first * AD + col;
+                    for (int r = r0; r < r1; ++r) {
+                        const double xv = (double)xc[(int64_t)r * AD];
+                        // uj0 is a multiple of JT >= 8 floats, the row pitch of 16 bytes
+                        const float4 *__restrict__ dh =
+                            reinterpret_cast<const float4 *>(s_h + r * kHPad + uj0);
+    #pragma unroll
+                        for (int i = 0; i < JT / 4; ++i) {
+                            const float4 d4 = dh[i];
+                            acc[4 * i] = __builtin_fma((double)d4.x, xv, acc[4 * i]);
+                            acc[4 * i + 1] = __builtin_fma((double)d4.y, xv, acc[4 * i + 1]);
+                            acc[4 * i + 2] = __builtin_fma((double)d4.z, xv, acc[4 * i + 2]);
+                            acc[4 * i + 3] = __builtin_fma((double)d4.w, xv, acc[4 * i + 3]);
+                        }
+                    }
+                };
+                const bool one = wk.R >= kCriticTile;  // at most one step boundary
+                const int64_t run0 = wk.run0();
+                const int n0 = one && run0 < nrows ? (int)run0 : nrows;
+                if (JT <= 8 && one) {
+                    // two constant-stride runs
+                    add_rows(0, n0, wk.first0());
+                    add_rows(n0, nrows, wk.first1());
+                } else {
+                    // one copy of the loop (JT = 64: 64 accumulators per copy); r is
+                    // block-uniform, so the choice of the base is scalar work
+                    for (int r = 0; r < nrows; ++r)
+                        add_rows(r, r + 1,
+                                 one ? (r < n0 ? wk.first0() : wk.first1()) : wk.at(r) - r);
+                }
+            } else {
+                const float *__restrict__ xc = g.b.obs + tile * AD + col;
+                for (int r = 0; r < nrows; ++r) {
+                    const double xv = (double)xc[(int64_t)r * AD];
+                    // uj0 is a multiple of JT >= 8 floats, the row pitch of 16 bytes
+                    const float4 *__restrict__ dh =
+                        reinterpret_cast<const float4 *>(s_h + r * kHPad + uj0);
 #pragma unroll
-                for (int i = 0; i < JT / 4; ++i) {
-                    const float4 d4 = dh[i];
-                    acc[4 * i] = __builtin_fma((double)d4.x, xv, acc[4 * i]);
-                    acc[4 * i + 1] = __builtin_fma((double)d4.y, xv, acc[4 * i + 1]);
-                    acc[4 * i + 2] = __builtin_fma((double)d4.z, xv, acc[4 * i + 2]);
-                    acc[4 * i + 3] = __builtin_fma((double)d4.w, xv, acc[4 * i + 3]);
+                    for (int i = 0; i < JT / 4; ++i) {
+                        const float4 d4 = dh[i];
+                        acc[4 * i] = __builtin_fma((double)d4.x, xv, acc[4 * i]);
+                        acc[4 * i + 1] = __builtin_fma((double)d4.y, xv, acc[4 * i + 1]);
+                        acc[4 * i + 2] = __builtin_fma((double)d4.z, xv, acc[4 * i + 2]);
+                        acc[4 * i + 3] = __builtin_fma((double)d4.w, xv, acc[4 * i + 3]);
+                    }
                 }
             }
         }
@@ -1189,7 +1343,8 @@ int check_critic_bufs(const MarlnavPpoBuffers *b)
 // marlnav_ppo_actor_grad; given: the same two with the Adam step folded in.
 int enqueue_actor(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
                   double ent_const, int advantage_mode, const AdvArgs *adv, const FoldArgs *fold,
-                  hipStream_t s, const ClipFoldArgs *clip = nullptr, const DiagArgs *dg = nullptr)
+                  hipStream_t s, const ClipFoldArgs *clip = nullptr, const DiagArgs *dg = nullptr,
+                  const int32_t *steps = nullptr)
 {
     PpoArgs a = make_args(d, b);
     actor_grid(a.M, a.rows_per_block, a.nblocks);
@@ -1204,37 +1359,49 @@ int enqueue_actor(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double ep
     const dim3 grid((unsigned)a.nblocks), blk(kThreads);
     const size_t lds = actor_lds_bytes(a.D);
     const bool env = advantage_mode == MARLNAV_ADVANTAGE_ENV;
-    if (dg) {  // the diagnostic variant (adv, fold, clip are NULL)
-        const size_t dg_lds = fin_lds + sizeof(double) * kWaves;
+    // the pass launch over `g` (PpoArgs, or GatherArgs: the gather variant) with
+    // the trailing pack x
+    auto pass = [&](const auto &g, auto... x) {
         if (env)
-            hipLaunchKernelGGL((actor_pass<kPairEnv>), grid, blk, lds, s, a, *dg);
+            hipLaunchKernelGGL((actor_pass<kPairEnv>), grid, blk, lds, s, g, x...);
         else
-            hipLaunchKernelGGL((actor_pass<kPairReference>), grid, blk, lds, s, a, *dg);
-        hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), dg_lds, s, a, *dg);
+            hipLaunchKernelGGL((actor_pass<kPairReference>), grid, blk, lds, s, g, x...);
+    };
+    // the finish launches read the workspace alone: they take PpoArgs always
+    auto finish = [&](size_t bytes, auto... x) {
+        hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), bytes, s, a, x...);
+    };
+    const size_t dg_lds = fin_lds + sizeof(double) * kWaves;
+    if (steps) {  // the gather variants (adv, fold, clip are NULL): nothing is folded
+        GatherArgs ga;
+        static_cast<PpoArgs &>(ga) = a;
+        ga.steps = steps;
+        if (dg) {
+            pass(ga, *dg);
+            finish(dg_lds, *dg);
+        } else {
+            pass(ga);
+            finish(fin_lds);
+        }
+    } else if (dg) {  // the diagnostic variant (adv, fold, clip are NULL)
+        pass(a, *dg);
+        finish(dg_lds, *dg);
     } else if (clip) {  // the clipped update folded in (fold is NULL)
-        if (env)
-            hipLaunchKernelGGL((actor_pass<kPairEnv>), grid, blk, lds, s, a, *adv);
-        else
-            hipLaunchKernelGGL((actor_pass<kPairReference>), grid, blk, lds, s, a, *adv);
-        hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), fin_lds, s, a, *clip);
+        pass(a, *adv);
+        finish(fin_lds, *clip);
     } else if (fold) {
-        if (env)
-            hipLaunchKernelGGL((actor_pass<kPairEnv>), grid, blk, lds, s, a, *adv);
-        else
-            hipLaunchKernelGGL((actor_pass<kPairReference>), grid, blk, lds, s, a, *adv);
-        hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), fin_lds, s, a, *fold);
+        pass(a, *adv);
+        finish(fin_lds, *fold);
     } else {
-        if (env)
-            hipLaunchKernelGGL((actor_pass<kPairEnv>), grid, blk, lds, s, a);
-        else
-            hipLaunchKernelGGL((actor_pass<kPairReference>), grid, blk, lds, s, a);
-        hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), fin_lds, s, a);
+        pass(a);
+        finish(fin_lds);
     }
     return launch_status();
 }
 
 int enqueue_critic(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
-                   const AdvArgs *adv, const FoldArgs *fold, hipStream_t s)
+                   const AdvArgs *adv, const FoldArgs *fold, hipStream_t s,
+                   const int32_t *steps = nullptr)
 {
     PpoArgs a = make_args(d, b);
     const int AD = a.A * a.D;
@@ -1242,47 +1409,57 @@ int enqueue_critic(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double e
     critic_grid(a.N, AD, a.H, ct, a.rows_per_block, a.nblocks);
     a.eps_f = (float)epsilon;  // values - epsilon: a Python scalar against an fp32 tensor
     const dim3 grid((unsigned)a.nblocks, (unsigned)(ct.ncoltile * ct.nugroup));
+    // (with a gather too: every step starts a multiple of P A D floats after step 0)
     const int vec4 = AD % 4 == 0 && (reinterpret_cast<uintptr_t>(b->obs) & 15u) == 0;
-    if (critic_split(a.N, a.H, ct)) {
+    const bool split = critic_split(a.N, a.H, ct);
+    CriticTiling fw = ct;
+    float *dhbuf = nullptr;
+    int hp = 0;
+    dim3 fgrid(1);
+    if (split) {
         // forward once per row: blocks of 64 hidden units, no output tile
-        CriticTiling fw = ct;
         fw.kc = AD < kThreads ? AD : kThreads;
         fw.ncoltile = 1;
         fw.us_n = 1;
         fw.jt = 64;
         fw.ub = 64;
         fw.nugroup = (a.H + 63) / 64;
-        const int hp = dh_pitch(a.H);
+        hp = dh_pitch(a.H);
         critic_forward_grid(a.N, a.fw_rows, a.fw_blocks);
         a.fw_part = b->work + a.nblocks * critic_stride(AD, a.H);
-        float *dhbuf = reinterpret_cast<float *>(a.fw_part + a.fw_blocks * (2 * a.H + 2));
-        const dim3 fgrid((unsigned)a.fw_blocks, (unsigned)fw.nugroup);
-        if (fold)
-            hipLaunchKernelGGL((critic_pass<1, kForward>), fgrid, dim3(kThreads),
-                               kCriticLdsBytes, s, a, fw, dhbuf, hp, vec4, *adv);
-        else
-            hipLaunchKernelGGL((critic_pass<1, kForward>), fgrid, dim3(kThreads), kCriticLdsBytes,
-                               s, a, fw, dhbuf, hp, vec4);
-        if (ct.jt == 8)
-            hipLaunchKernelGGL((critic_pass<8, kBackward>), grid, dim3(kThreads), kCriticLdsBytes,
-                               s, a, ct, dhbuf, hp, vec4);
-        else
-            hipLaunchKernelGGL((critic_pass<64, kBackward>), grid, dim3(kThreads), kCriticLdsBytes,
-                               s, a, ct, dhbuf, hp, vec4);
-    } else if (ct.jt == 8) {
-        if (fold)
-            hipLaunchKernelGGL((critic_pass<8, kFused>), grid, dim3(kThreads), kCriticLdsBytes,
-                               s, a, ct, (float *)nullptr, 0, vec4, *adv);
-        else
-            hipLaunchKernelGGL((critic_pass<8, kFused>), grid, dim3(kThreads), kCriticLdsBytes, s,
-                               a, ct, (float *)nullptr, 0, vec4);
+        dhbuf = reinterpret_cast<float *>(a.fw_part + a.fw_blocks * (2 * a.H + 2));
+        fgrid = dim3((unsigned)a.fw_blocks, (unsigned)fw.nugroup);
+    }
+    // the pass launches over `g` (PpoArgs, or GatherArgs: the gather variants);
+    // x: empty, or the AdvArgs of a folded update for the update's first launch
+    auto pass = [&](const auto &g, auto... x) {
+        const dim3 blk(kThreads);
+        if (split) {
+            hipLaunchKernelGGL((critic_pass<1, kForward>), fgrid, blk, kCriticLdsBytes, s, g, fw,
+                               dhbuf, hp, vec4, x...);
+            if (ct.jt == 8)
+                hipLaunchKernelGGL((critic_pass<8, kBackward>), grid, blk, kCriticLdsBytes, s, g,
+                                   ct, dhbuf, hp, vec4);
+            else
+                hipLaunchKernelGGL((critic_pass<64, kBackward>), grid, blk, kCriticLdsBytes, s, g,
+                                   ct, dhbuf, hp, vec4);
+        } else if (ct.jt == 8) {
+            hipLaunchKernelGGL((critic_pass<8, kFused>), grid, blk, kCriticLdsBytes, s, g, ct,
+                               (float *)nullptr, 0, vec4, x...);
+        } else {
+            hipLaunchKernelGGL((critic_pass<64, kFused>), grid, blk, kCriticLdsBytes, s, g, ct,
+                               (float *)nullptr, 0, vec4, x...);
+        }
+    };
+    if (steps) {  // adv, fold are NULL: nothing is folded
+        GatherArgs ga;
+        static_cast<PpoArgs &>(ga) = a;
+        ga.steps = steps;
+        pass(ga);
+    } else if (fold) {
+        pass(a, *adv);
     } else {
-        if (fold)
-            hipLaunchKernelGGL((critic_pass<64, kFused>), grid, dim3(kThreads), kCriticLdsBytes,
-                               s, a, ct, (float *)nullptr, 0, vec4, *adv);
-        else
-            hipLaunchKernelGGL((critic_pass<64, kFused>), grid, dim3(kThreads), kCriticLdsBytes, s,
-                               a, ct, (float *)nullptr, 0, vec4);
+        pass(a);
     }
     const int64_t nout = critic_stride(AD, a.H);
     const dim3 ogrid((unsigned)((nout + kThreads - 1) / kThreads));
@@ -1337,6 +1514,72 @@ __attribute__((visibility("hidden"))) int marlnav_internal_ppo_actor_diag(
     const DiagArgs dg = {diag_row, stop, target_kl, k, k == 0 ? 1 : 0};
     return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
                          (hipStream_t)stream, nullptr, &dg);
+}
+
+namespace {
+
+int check_steps(const int32_t *steps)
+{
+    if (!steps) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: steps is NULL");
+    if (reinterpret_cast<uintptr_t>(steps) & 3u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: steps must be 4-byte aligned");
+    return 0;
+}
+
+}  // namespace
+
+// The gather forms: logical step slot s of the minibatch is
+// step steps[s] of the storage whose step 0 the data pointers address.
+extern "C" int marlnav_ppo_actor_grad_steps(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                                            const int32_t *steps, double epsilon,
+                                            double ent_const, int advantage_mode, double *diag,
+                                            void *stream)
+{
+    int rc = check_dims(d);
+    if (rc) return rc;
+    rc = check_mode(advantage_mode);
+    if (rc) return rc;
+    rc = check_actor_bufs(b, advantage_mode);
+    if (rc) return rc;
+    rc = check_steps(steps);
+    if (rc) return rc;
+    if (reinterpret_cast<uintptr_t>(diag) & 7u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: diag must be 8-byte aligned");
+    const DiagArgs dg = {diag, nullptr, __builtin_inf(), 0, 1};
+    return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
+                         (hipStream_t)stream, nullptr, diag ? &dg : nullptr, steps);
+}
+
+extern "C" int marlnav_ppo_critic_grad_steps(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                                             const int32_t *steps, double epsilon, void *stream)
+{
+    int rc = check_dims(d);
+    if (rc) return rc;
+    rc = check_critic_bufs(b);
+    if (rc) return rc;
+    rc = check_steps(steps);
+    if (rc) return rc;
+    return enqueue_critic(d, b, epsilon, nullptr, nullptr, (hipStream_t)stream, steps);
+}
+
+// Update k of marlnav_ppo_train_phase_shuffled (marlnav_adam.hip, which has
+// checked every argument): the gather gradient launches of one minibatch; with
+// diag_row the diagnostic variant and the stop, as marlnav_internal_ppo_actor_diag.
+// check_only: the dims and buffer checks and nothing launched.
+__attribute__((visibility("hidden"))) int marlnav_internal_ppo_grad_steps(
+    int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, const int32_t *steps,
+    double epsilon, double ent_const, int advantage_mode, double *diag_row, int64_t *stop,
+    double target_kl, int64_t k, void *stream, int check_only)
+{
+    int rc = check_dims(d);
+    if (rc) return rc;
+    rc = network == 0 ? check_actor_bufs(b, advantage_mode) : check_critic_bufs(b);
+    if (rc || check_only) return rc;
+    if (network != 0)
+        return enqueue_critic(d, b, epsilon, nullptr, nullptr, (hipStream_t)stream, steps);
+    const DiagArgs dg = {diag_row, stop, target_kl, k, k == 0 ? 1 : 0};
+    return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
+                         (hipStream_t)stream, nullptr, diag_row ? &dg : nullptr, steps);
 }
 
 extern "C" int marlnav_ppo_actor_grad(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,

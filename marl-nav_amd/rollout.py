@@ -570,6 +570,73 @@ def minibatch_bounds(buffer_len, batch_size):
     return out
 
 
+def shuffled_minibatch_sizes(buffer_len, batch_size):
+    """The step counts of one epoch's minibatches in the shuffled mode
+    (DESIGN.md §18): ``buffer_len // batch_size`` minibatches of
+    ``batch_size`` steps of the epoch's permutation, the last one extended by
+    the ``buffer_len % batch_size`` left over, so the sizes sum to
+    ``buffer_len`` and every stored step is used once per epoch. No minibatch
+    (``batch_size > buffer_len``) is a ValueError."""
+    buffer_len, batch_size = int(buffer_len), int(batch_size)
+    if batch_size < 1 or buffer_len < 1:
+        raise ValueError(f"buffer_len={buffer_len} and batch_size={batch_size} must be >= 1")
+    n = buffer_len // batch_size
+    if n == 0:
+        raise ValueError(f"batch_size={batch_size} is greater than the {buffer_len} stored "
+                         "steps: no minibatch")
+    return [batch_size] * (n - 1) + [buffer_len - (n - 1) * batch_size]
+
+
+def shuffled_minibatches(perm, batch_size):
+    """One epoch's minibatches as lists of steps: ``perm`` (a sequence of
+    ``buffer_len`` steps) cut by ``shuffled_minibatch_sizes``."""
+    perm = [int(x) for x in perm]
+    out, at = [], 0
+    for n in shuffled_minibatch_sizes(len(perm), batch_size):
+        out.append(perm[at:at + n])
+        at += n
+    return out
+
+
+def check_shuffle_len(buffer_len, num_epochs=1):
+    """ValueError unless the on-device permutation generator takes a buffer
+    of ``buffer_len`` steps over ``num_epochs`` epochs (both at most 65 535:
+    ``marlnav_minibatch_permutations``)."""
+    if not 1 <= int(buffer_len) <= abi.SHUFFLE_MAX_STEPS:
+        raise ValueError(f"shuffled minibatches take 1..{abi.SHUFFLE_MAX_STEPS} stored steps, "
+                         f"got {buffer_len}")
+    if not 1 <= int(num_epochs) <= abi.SHUFFLE_MAX_STEPS:
+        raise ValueError(f"shuffled minibatches take 1..{abi.SHUFFLE_MAX_STEPS} epochs, "
+                         f"got {num_epochs}")
+
+
+def check_steps(steps, stored):
+    """A minibatch's step list as a list of ints: a non-empty HOST sequence or
+    CPU integer tensor with every entry in ``[0, stored)`` (duplicates are
+    allowed); anything else is a ValueError. A device tensor is refused: its
+    entries would reach the kernels unchecked."""
+    if torch.is_tensor(steps):
+        if steps.device.type != 'cpu':
+            raise ValueError("steps: need a host sequence or a CPU integer tensor, got a tensor "
+                             f"on {steps.device}; device-side step tables are drawn and used by "
+                             "training.train_phase(shuffle=...) only")
+        if steps.dtype.is_floating_point or steps.dtype == torch.bool or steps.dim() != 1:
+            raise ValueError(f"steps: need a 1-d integer tensor, got {steps.dtype} "
+                             f"{tuple(steps.shape)}")
+        steps = steps.tolist()
+    out = []
+    for x in steps:
+        if isinstance(x, bool) or int(x) != x:
+            raise ValueError(f"steps: {x!r} is not an integer")
+        out.append(int(x))
+    if not out:
+        raise ValueError("steps is empty: a minibatch needs at least one step")
+    for x in out:
+        if not 0 <= x < stored:
+            raise ValueError(f"steps: {x} is outside the {stored} stored steps [0, {stored})")
+    return out
+
+
 class FusedPPO(object):
     """``MAPPO._actor_loss`` / ``_critic_loss`` (models.py:270-316) of one
     minibatch with ``zero_grad()`` + ``backward()`` (models.py:173-175,
@@ -611,6 +678,8 @@ class FusedPPO(object):
         self._bufs = abi.MarlnavPpoBuffers()
         self._work = None
         self.last_diag = self.last_stop = None     # of the last monitored train_phase
+        # train_phase(shuffle=...): per network the call counter cell and the last table
+        self._shuffle_counter, self.last_steps = {}, {}
         for f, t in self._params:
             if t.grad is None:
                 t.grad = torch.zeros_like(t)
@@ -710,6 +779,76 @@ class FusedPPO(object):
         abi.check(self._lib.marlnav_ppo_critic_grad(
             ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon,
             _stream(self.device)), self._lib)
+        return loss
+
+    def _bind_steps(self, buffer, steps, network='actor', diag=False):
+        """``_bind`` for a minibatch given as a list of steps: the data
+        pointers at step 0 of the storage, ``num_steps`` the length of the
+        list, the list uploaded as an int32 device table; -> (loss, table)."""
+        steps = check_steps(steps, len(buffer))
+        loss = self._bind(buffer, 0, len(buffer), network, diag)
+        d, b = self._dims, self._bufs
+        d.num_steps = len(steps)
+        size = self._lib.marlnav_ppo_diag_work_size if diag else self._lib.marlnav_ppo_work_size
+        need = int(size(ctypes.byref(d)))
+        if need < 0:
+            abi.check(need, self._lib)
+        if self._work.numel() < need:
+            self._work = torch.empty(need, dtype=_F64, device=self.device)
+        b.work = self._work.data_ptr()
+        table = torch.tensor(steps, dtype=torch.int32).to(self.device)
+        return loss, table
+
+    def actor_loss_grad_steps(self, buffer, steps, diag_out=None):
+        """``actor_loss_grad`` of the minibatch whose steps are ``steps`` in
+        that order (``marlnav_ppo_actor_grad_steps``): logical
+        row ``(slot, p, a)`` is the agent row of step ``steps[slot]``. Bit for
+        bit ``actor_loss_grad(gathered, 0, len(steps))`` on a buffer whose
+        storage was gathered with ``index_select(0, steps)``; the kernels
+        gather by address and copy nothing.
+
+        ``steps``: a host sequence or CPU integer tensor, non-empty, every
+        entry in ``[0, len(buffer))``, duplicates allowed; checked here and
+        uploaded as int32 (a host-to-device copy: not for graph capture). A
+        device tensor is a ValueError: ``training.train_phase(shuffle=...)``
+        is the path whose tables never leave the device."""
+        if diag_out is not None:
+            check_diag_out(diag_out, self.device)
+        loss, table = self._bind_steps(buffer, steps, 'actor', diag=diag_out is not None)
+        abi.check(self._lib.marlnav_ppo_actor_grad_steps(
+            ctypes.byref(self._dims), ctypes.byref(self._bufs), table.data_ptr(), self.epsilon,
+            self.ent_const, self._mode, None if diag_out is None else diag_out.data_ptr(),
+            _stream(self.device)), self._lib)
+        return loss
+
+    def critic_loss_grad_steps(self, buffer, steps):
+        """``critic_loss_grad`` of the minibatch ``steps``
+        (``marlnav_ppo_critic_grad_steps``), as ``actor_loss_grad_steps``."""
+        loss, table = self._bind_steps(buffer, steps, 'critic')
+        abi.check(self._lib.marlnav_ppo_critic_grad_steps(
+            ctypes.byref(self._dims), ctypes.byref(self._bufs), table.data_ptr(), self.epsilon,
+            _stream(self.device)), self._lib)
+        return loss
+
+    def actor_update_steps(self, buffer, steps, adam, max_grad_norm=None, norm_out=None):
+        """``actor_loss_grad_steps(buffer, steps)`` then
+        ``adam.step(max_grad_norm, norm_out)``: the unfolded update that
+        ``train_phase(shuffle=...)`` enqueues per minibatch. ``adam``: a
+        ``FusedAdam`` over exactly the six actor parameters in order.
+        Returns the loss."""
+        if not (isinstance(adam, FusedAdam) and adam.covers(self._network_params("actor"))):
+            raise ValueError("adam: need a FusedAdam over exactly the actor's parameters in order")
+        loss = self.actor_loss_grad_steps(buffer, steps)
+        adam.step(max_grad_norm=max_grad_norm, norm_out=norm_out)
+        return loss
+
+    def critic_update_steps(self, buffer, steps, adam, max_grad_norm=None, norm_out=None):
+        """As ``actor_update_steps``, for the critic."""
+        if not (isinstance(adam, FusedAdam) and adam.covers(self._network_params("critic"))):
+            raise ValueError("adam: need a FusedAdam over exactly the critic's parameters in "
+                             "order")
+        loss = self.critic_loss_grad_steps(buffer, steps)
+        adam.step(max_grad_norm=max_grad_norm, norm_out=norm_out)
         return loss
 
     def _network_params(self, which):
@@ -1025,6 +1164,45 @@ def check_diag_out(diag_out, device, rows=1, what="diag_out"):
         raise ValueError(f"{what}: need a contiguous float64 tensor of {n} elements on {device}")
 
 
+def _train_steps(ppo, update_steps, network, buffer, optimizer, num_epochs, batch_size, log,
+                 max_grad_norm, norm_log, steps_table):
+    """The shuffled mode's host loop: row e of ``steps_table`` is epoch e's
+    permutation, cut by ``shuffled_minibatches``; one ``*_update_steps`` per
+    minibatch."""
+    ppo._require(buffer)
+    if torch.is_tensor(steps_table):
+        if steps_table.device.type != 'cpu':
+            raise ValueError("steps_table: need a host (E, L) array, got a tensor on "
+                             f"{steps_table.device} (copy ppo.last_steps[...] to the host)")
+        steps_table = steps_table.tolist()
+    rows = [list(r) for r in steps_table]
+    if len(rows) != int(num_epochs) or any(len(r) != len(buffer) for r in rows):
+        raise ValueError(f"steps_table: need {int(num_epochs)} rows of {len(buffer)} steps")
+    if not (isinstance(optimizer, FusedAdam) and optimizer.covers(network)):
+        raise ValueError("steps_table needs a FusedAdam over exactly this network's parameters "
+                         "in order")
+    if max_grad_norm is None:
+        if norm_log is not None:
+            raise ValueError("norm_log needs max_grad_norm (inf records the norms only)")
+    else:
+        check_max_grad_norm(max_grad_norm)
+    cells, k = None, 0
+    if norm_log is not None:
+        cells = torch.empty(len(rows) * (len(buffer) // int(batch_size)), dtype=_F64,
+                            device=ppo.device)
+    for perm in rows:
+        for steps in shuffled_minibatches(perm, batch_size):
+            norm = None
+            if cells is not None:
+                norm = cells[k]
+                norm_log.append(norm)
+                k += 1
+            loss = update_steps(buffer, steps, optimizer, max_grad_norm=max_grad_norm,
+                                norm_out=norm)
+            if log is not None:
+                log.append(loss)
+
+
 def _train(ppo, loss_grad, update, network, buffer, optimizer, num_epochs, batch_size, log,
            max_grad_norm=None, norm_log=None):
     ppo._require(buffer)
@@ -1064,7 +1242,7 @@ def _train(ppo, loss_grad, update, network, buffer, optimizer, num_epochs, batch
 
 
 def train_actor(ppo, buffer, optimizer, num_epochs, batch_size, log=None, max_grad_norm=None,
-                norm_log=None):
+                norm_log=None, steps_table=None):
     """MAPPO.train_actor (models.py:160-178): per epoch and minibatch
     (``minibatch_bounds``) the fused loss and gradients, ``optimizer.step()``,
     then ``log.append(loss)`` with the loss left on the device. ``optimizer``
@@ -1081,13 +1259,30 @@ def train_actor(ppo, buffer, optimizer, num_epochs, batch_size, log=None, max_gr
     the global L2 norm first (``ppo.actor_update(..., max_grad_norm=...)``,
     DESIGN.md §16) and, with a list ``norm_log``, appends the norm before
     clipping (0-d float64 device tensor). This needs that ``FusedAdam``: with
-    any other optimiser it is a ValueError."""
+    any other optimiser it is a ValueError.
+
+    ``steps_table`` (None: the above): a host ``(num_epochs, len(buffer))``
+    array of steps, row e the permutation of epoch e. The
+    epochs then run over the minibatches of ``shuffled_minibatches(row,
+    batch_size)``, one ``ppo.actor_update_steps`` each, and use every stored
+    step once per epoch: the host loop that ``training.train_phase(...,
+    shuffle=seed)`` equals bit for bit when given its
+    ``ppo.last_steps['actor']``. Needs that ``FusedAdam`` too."""
+    if steps_table is not None:
+        return _train_steps(ppo, ppo.actor_update_steps, ppo._network_params("actor"), buffer,
+                            optimizer, num_epochs, batch_size, log, max_grad_norm, norm_log,
+                            steps_table)
     _train(ppo, ppo.actor_loss_grad, ppo.actor_update, ppo._network_params("actor"), buffer,
            optimizer, num_epochs, batch_size, log, max_grad_norm, norm_log)
 
 
 def train_critic(ppo, buffer, optimizer, num_epochs, batch_size, log=None, max_grad_norm=None,
-                 norm_log=None):
-    """MAPPO.train_critic (models.py:180-198), as ``train_actor``."""
+                 norm_log=None, steps_table=None):
+    """MAPPO.train_critic (models.py:180-198), as ``train_actor``
+    (``steps_table`` included: ``ppo.critic_update_steps``)."""
+    if steps_table is not None:
+        return _train_steps(ppo, ppo.critic_update_steps, ppo._network_params("critic"), buffer,
+                            optimizer, num_epochs, batch_size, log, max_grad_norm, norm_log,
+                            steps_table)
     _train(ppo, ppo.critic_loss_grad, ppo.critic_update, ppo._network_params("critic"), buffer,
            optimizer, num_epochs, batch_size, log, max_grad_norm, norm_log)

@@ -29,7 +29,8 @@ import torch
 from torch import nn
 
 from . import abi, rollout
-from .rollout import FusedAdam, FusedPolicy, FusedPPO, RolloutBuffer, minibatch_bounds
+from .rollout import (FusedAdam, FusedPolicy, FusedPPO, RolloutBuffer, minibatch_bounds,
+                      shuffled_minibatch_sizes)
 from .utils import ActionScaler, ObsNormalizer
 
 _F64 = torch.float64
@@ -191,7 +192,7 @@ def write_stats(logs, full_params, out_dir, stamp, plot=True):
 
 
 def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None, max_grad_norm=None,
-                norm_out=None, target_kl=None, diag_out=None, stop_out=None):
+                norm_out=None, target_kl=None, diag_out=None, stop_out=None, shuffle=None):
     """One whole ``train_actor`` (``network='actor'``) or ``train_critic``
     (``'critic'``) of the reference (models.py:160-198) over ``buffer`` as ONE
     C call, libmarlnav.so ``marlnav_ppo_train_phase``: ``num_epochs`` times
@@ -234,7 +235,28 @@ def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None, ma
     the count carry the bits of the unmonitored call. Composes with
     ``max_grad_norm`` and both advantage modes. The rows and the cell are kept
     as ``ppo.last_diag`` / ``ppo.last_stop``. ``network='critic'`` with any of
-    the three is a ValueError."""
+    the three is a ValueError.
+
+    ``shuffle`` (None: the above, bit for bit): an int seed selects the
+    shuffled mode (one ``marlnav_ppo_train_phase_shuffled``).
+    One launch draws a fresh uniform permutation of ALL ``len(buffer)`` stored
+    steps per epoch, on the device; minibatch j of an epoch is entries ``[j
+    batch_size, (j + 1) batch_size)`` of its permutation, the last one extended
+    by the ``len(buffer) % batch_size`` left over
+    (``rollout.shuffled_minibatch_sizes``), so every stored step, the final one
+    included, is used exactly once per epoch. The number of updates and every
+    log's layout stay as they are. The kernels gather the steps by address and
+    copy nothing; an update is the gradient launches and ``FusedAdam.step``'s
+    (this mode has no folded finish launches). The permutations are keyed by
+    the seed, the network, the epoch and a call counter that lives on the
+    device (one cell per network on ``ppo``, created zero at first use and
+    advanced by the launch), so a captured graph draws new permutations at
+    every replay. The table of the last call, ``(num_epochs, len(buffer))``
+    int32 on the device, is ``ppo.last_steps['actor' | 'critic']``: with it
+    ``rollout.train_actor`` / ``train_critic(..., steps_table=...)`` repeat
+    the phase bit for bit. Composes with ``max_grad_norm``, ``target_kl`` /
+    ``diag_out`` and both advantage modes. At most 65 535 stored steps and
+    epochs."""
     nets = {'actor': abi.NETWORK_ACTOR, 'critic': abi.NETWORK_CRITIC,
             abi.NETWORK_ACTOR: abi.NETWORK_ACTOR, abi.NETWORK_CRITIC: abi.NETWORK_CRITIC}
     if network not in nets:
@@ -247,7 +269,13 @@ def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None, ma
         target_kl = float('inf') if target_kl is None else rollout.check_target_kl(target_kl)
     ppo._require(buffer)
     lib, dev = ppo._lib, ppo.device
-    bounds = minibatch_bounds(len(buffer), batch_size)
+    if shuffle is not None:
+        if isinstance(shuffle, bool) or not isinstance(shuffle, int):
+            raise ValueError(f"shuffle: need an int seed or None, got {shuffle!r}")
+        bounds = shuffled_minibatch_sizes(len(buffer), batch_size)
+        rollout.check_shuffle_len(len(buffer), num_epochs)
+    else:
+        bounds = minibatch_bounds(len(buffer), batch_size)
     B, E = len(bounds), int(num_epochs)
     if B < 1:
         raise ValueError(f"batch_size={batch_size} is greater than the {len(buffer)} stored "
@@ -269,10 +297,15 @@ def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None, ma
                 or stop_out.device != dev or stop_out.numel() != 2
                 or not stop_out.is_contiguous()):
             raise ValueError(f"stop_out: need a contiguous int64 tensor of 2 elements on {dev}")
-    arr = (ctypes.c_int64 * (2 * B))(*[x for b in bounds for x in b])
     # step 0 of the storage, dims of the whole buffer
-    ppo._bind(buffer, 0, len(buffer), 'actor' if nets[network] == abi.NETWORK_ACTOR else 'critic')
+    name = 'actor' if nets[network] == abi.NETWORK_ACTOR else 'critic'
+    ppo._bind(buffer, 0, len(buffer), name)
     d, b = ppo._dims, ppo._bufs
+    if shuffle is not None:
+        return _shuffled_phase(ppo, adam, name, nets[network], int(batch_size), E, B, out,
+                               max_grad_norm, norm_out, monitored, target_kl, diag_out, stop_out,
+                               shuffle)
+    arr = (ctypes.c_int64 * (2 * B))(*[x for b in bounds for x in b])
     size = lib.marlnav_ppo_train_diag_work_size if monitored else lib.marlnav_ppo_train_work_size
     need = int(size(ctypes.byref(d), arr, B))
     if need < 0:
@@ -308,6 +341,46 @@ def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None, ma
         nets[network], ctypes.byref(d), ctypes.byref(b), arr, B, E, ppo.epsilon, ppo.ent_const,
         ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(), ppo._mode, g, work, norms,
         torch._C._cuda_getCurrentRawStream(dev.index)), lib)
+    return out
+
+
+def _shuffled_phase(ppo, adam, name, network, batch_size, E, B, out, max_grad_norm, norm_out,
+                    monitored, target_kl, diag_out, stop_out, seed):
+    """``train_phase(shuffle=seed)`` behind its checks: ``ppo``'s structs are
+    bound to the whole buffer."""
+    lib, dev = ppo._lib, ppo.device
+    d, b = ppo._dims, ppo._bufs
+    L = int(d.num_steps)
+    need = int(lib.marlnav_ppo_train_shuffled_work_size(ctypes.byref(d), batch_size,
+                                                        1 if monitored else 0))
+    if need < 0:
+        abi.check(need, lib)
+    if ppo._work.numel() < need:
+        ppo._work = torch.empty(need, dtype=_F64, device=dev)
+    b.work = ppo._work.data_ptr()
+    # the call counter and the table live on ppo: a captured graph keeps their pointers
+    if name not in ppo._shuffle_counter:
+        ppo._shuffle_counter[name] = torch.zeros(1, dtype=torch.int64, device=dev)
+    counter = ppo._shuffle_counter[name]
+    table = ppo.last_steps.get(name)
+    if table is None or tuple(table.shape) != (E, L):
+        table = torch.zeros(E, L, dtype=torch.int32, device=dev)
+    ppo.last_steps[name] = table
+    ad, ab = adam._bind()
+    if max_grad_norm is None:
+        if norm_out is not None:
+            raise ValueError("norm_out needs max_grad_norm (inf records the norms only)")
+        g, work, norms = abi.MAX_NORM_NONE, None, None
+    else:
+        g, work, norms = adam._clip_args(max_grad_norm, norm_out, count=E * B)
+    abi.check(lib.marlnav_ppo_train_phase_shuffled(
+        network, ctypes.byref(d), ctypes.byref(b), batch_size, E, ppo.epsilon, ppo.ent_const,
+        ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(), ppo._mode, g, work, norms,
+        target_kl if monitored else 0.0, diag_out.data_ptr() if monitored else None,
+        stop_out.data_ptr() if monitored else None, seed & 0xFFFFFFFFFFFFFFFF,
+        counter.data_ptr(), table.data_ptr(), torch._C._cuda_getCurrentRawStream(dev.index)), lib)
+    if monitored:
+        ppo.last_diag, ppo.last_stop = diag_out, stop_out
     return out
 
 
@@ -348,6 +421,15 @@ class MAPPO(object):
     ``actor_stopped_at`` (one int per rollout, -1 where the phase ran to its
     end); the loss of an update behind a stop is NaN.
 
+    ``params['shuffle_minibatches']`` (a bool; absent or False: today's
+    behaviour bit for bit) trains both phases on fresh random minibatches
+    (DESIGN.md §18): per epoch a new uniform permutation of all ``buffer_len``
+    stored steps, drawn on the device and keyed by ``seed``, is cut into the
+    ``buffer_len // batch_size`` minibatches, the last one taking the steps
+    left over, so the buffer's final step, which the reference's slices drop,
+    is trained on. The logs keep their layout; ``repeat()`` still does not
+    synchronise. The last tables are ``self.ppo.last_steps``.
+
     ``seed`` keys the policy kernel's normals (``FusedPolicy``); the modules'
     initial weights come from torch's global generator, as the reference's do.
 
@@ -379,6 +461,8 @@ class MAPPO(object):
             self.target_kl = rollout.check_target_kl(self.target_kl)
         self.log_diagnostics = bool(params.get('log_diagnostics'))
         self._monitored = self.target_kl is not None or self.log_diagnostics
+        self.shuffle_minibatches = bool(params.get('shuffle_minibatches'))
+        self._seed = int(seed)
         if env._rng != 'native' or env._init_sampler is not env._default_init_sampler:
             raise RuntimeError(f"{who} needs an env in native-RNG mode with its default init "
                                "sampler: a reference-RNG or user-assigned sampler is called on "
@@ -415,7 +499,11 @@ class MAPPO(object):
         self.batch_size = int(params['batch_size'])
         if self.num_epochs < 1:
             raise ValueError(f"num_epochs={self.num_epochs} must be >= 1")
-        self._bounds = minibatch_bounds(self.buffer_len, self.batch_size)
+        if self.shuffle_minibatches:    # as many updates; every stored step in some minibatch
+            self._bounds = shuffled_minibatch_sizes(self.buffer_len, self.batch_size)
+            rollout.check_shuffle_len(self.buffer_len, self.num_epochs)
+        else:
+            self._bounds = minibatch_bounds(self.buffer_len, self.batch_size)
         if not self._bounds:
             raise ValueError(f"batch_size={self.batch_size} is greater than "
                              f"buffer_len={self.buffer_len}: no minibatch")
@@ -577,7 +665,8 @@ class MAPPO(object):
                            stop_out=self._stop_log[r])
         train_phase(self.ppo, self.buffer, adam, network, self.num_epochs, self.batch_size,
                     out=log[r], max_grad_norm=self.max_grad_norm,
-                    norm_out=None if norm_log is None else norm_log[r], **monitor)
+                    norm_out=None if norm_log is None else norm_log[r],
+                    shuffle=self._seed if self.shuffle_minibatches else None, **monitor)
 
     def train_actor(self):
         """models.py:160-178 for the last rollout as ONE C call

@@ -186,6 +186,9 @@ def set_model_params(args, device):
         extra['target_kl'] = args.target_kl
     if getattr(args, 'log_diagnostics', False):
         extra['log_diagnostics'] = True
+    # marlnav_amd only: fresh shuffled minibatches per epoch, present only when asked for
+    if getattr(args, 'shuffle_minibatches', False):
+        extra['shuffle_minibatches'] = True
     return {
         'actor': {'input_size': obs_size, 'hidden_size': args.hidden_size},
         'critic': {'input_size': obs_size * args.num_agents, 'hidden_size': args.hidden_size},
