@@ -905,6 +905,29 @@ int marlnav_debug_force_family(int family);
  * this thread launched. */
 int marlnav_debug_last_family(void);
 
+/* Testing hook (not part of the reference's interface): the env-block step
+ * kernel also exists with its launch-invariant choices compiled in (every
+ * block full, native non-noisy re-init from a formation, no fused normaliser,
+ * no action scaler, default bond parameters, counters present), and
+ * marlnav_step launches that instantiation exactly when all of them hold.
+ * This restricts the choice, process-wide: AUTO (the default); GENERAL: never
+ * the specialised instantiation; FIXED_NO_DRAW: the specialised one whenever
+ * eligible, without the draw wave that grids of at most one block per
+ * compute unit otherwise add. Returns the previous setting, MARLNAV_EINVAL
+ * for an unknown mode. */
+#define MARLNAV_BLOCK_TRAITS_AUTO 0
+#define MARLNAV_BLOCK_TRAITS_GENERAL 1
+#define MARLNAV_BLOCK_TRAITS_FIXED_NO_DRAW 2
+int marlnav_debug_force_block_traits(int mode);
+
+/* What the last marlnav_step call on this thread launched: GENERAL (also for
+ * the other kernel families), FIXED (the specialised env-block step) or
+ * FIXED_DRAW (the same with the draw wave). */
+#define MARLNAV_BLOCK_RAN_GENERAL 0
+#define MARLNAV_BLOCK_RAN_FIXED 1
+#define MARLNAV_BLOCK_RAN_FIXED_DRAW 2
+int marlnav_debug_last_block_traits(void);
+
 /* Testing hook (not part of the reference's interface): the step kernels'
  * bearing acos (environment.py:286) of the n consecutive fp32 bit patterns
  * from `first`, into the device array out[n] (tests/golden/acos_dev_check.py

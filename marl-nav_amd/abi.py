@@ -195,6 +195,7 @@ EXPORTS = ("marlnav_step", "marlnav_observe", "marlnav_reinit_all", "marlnav_for
            "marlnav_ppo_train_phase_shuffled",
            "marlnav_last_error", "marlnav_abi_version",
            "marlnav_debug_force_family", "marlnav_debug_last_family",
+           "marlnav_debug_force_block_traits", "marlnav_debug_last_block_traits",
            "marlnav_debug_acos_range", "marlnav_debug_fastdiv_check")
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -347,6 +348,11 @@ def _declare(lib):
     lib.marlnav_debug_force_family.restype = c.c_int
     lib.marlnav_debug_last_family.argtypes = []
     lib.marlnav_debug_last_family.restype = c.c_int
+    if hasattr(lib, "marlnav_debug_force_block_traits"):  # (absent from A/B builds of older revisions)
+        lib.marlnav_debug_force_block_traits.argtypes = [c.c_int]
+        lib.marlnav_debug_force_block_traits.restype = c.c_int
+        lib.marlnav_debug_last_block_traits.argtypes = []
+        lib.marlnav_debug_last_block_traits.restype = c.c_int
     if hasattr(lib, "marlnav_debug_acos_range"):  # (absent from A/B builds of older revisions)
         lib.marlnav_debug_acos_range.argtypes = [c.c_uint32, c.c_int64, c.c_void_p, c.c_void_p]
         lib.marlnav_debug_acos_range.restype = c.c_int

@@ -189,6 +189,36 @@ __device__ __forceinline__ EnvEnd env_end(F flag, float step_num_old, uint8_t te
 template <int A, int O, bool HELP>
 constexpr bool kBlockEarlyOut = O >= 8 || !HELP;
 
+// The launch-invariant choices of block_kernel as a compile-time pack. Each
+// int member is -1 (unknown: tested at run time by every wave of every
+// launch), 0 or 1 (the host checked it: marlnav_step's selection rule, and
+// the test folds). BlockDynamic is the general instantiation; BlockFixed the
+// headline launch: every block full (P a multiple of 64), native non-noisy
+// re-init from a formation, no fused normaliser, no action scaler, the
+// default bond parameters (bond_sharpness 1, max_at_prop_d 2: the REFC
+// observation), counters with a slot per block, and written-through outputs
+// or not (WT). ptrs_early: the output pointers and the counter fields are
+// read from the kernarg segment before the observe barrier instead of after
+// it (their scalar-load latency under the barrier wait; still not live
+// across the observation, profiles/r05_ab_late_ptrs.txt).
+struct BlockDynamic {
+    static constexpr int all_full = -1, write_through = -1, native_overlap = -1,
+                         has_formation = -1, no_norm = -1, no_action_scale = -1,
+                         default_bond = -1, has_counters = -1;
+    static constexpr bool ptrs_early = false;
+};
+
+template <bool WT>
+struct BlockFixed {
+    static constexpr int all_full = 1, write_through = WT, native_overlap = 1, has_formation = 1,
+                         no_norm = 1, no_action_scale = 1, default_bond = 1, has_counters = 1;
+    static constexpr bool ptrs_early = true;
+};
+
+// A pack member V is read as `V < 0 ? <the run-time test> : V > 0`: the
+// condition is a constant, so only the chosen arm is compiled and the
+// general instantiation's code is what it was before the pack.
+
 // Phases (one block barrier after each of the first four): stage | move +
 // coordinate check | observe into LDS rows | per-env phase on wave 0 while
 // waves 1..A-1 re-initialise and re-observe the finished envs (native
@@ -197,7 +227,7 @@ constexpr bool kBlockEarlyOut = O >= 8 || !HELP;
 // 0's compute, tile 0's stores under tile 1's - measured bit-exact and
 // slower, 65536x3x3 6.44 -> 9.45 us: profiles/r06_ab_pipe.txt, code at
 // 16437ed.)
-template <int A, int O, bool OBS_ONLY, bool NOISY, bool HELP = false>
+template <int A, int O, bool OBS_ONLY, bool NOISY, bool HELP = false, class FX = BlockDynamic>
 __global__ void __launch_bounds__(64 * (A + HELP))
     block_kernel(float *h_states, const float *h_actions, const float *h_obstacles,
                  const float *h_target, const float *h_step_num, const uint8_t *h_terminates,
@@ -209,6 +239,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
     // only meets the barriers)
     constexpr int E = BP::E, R = BP::R, D = BP::D, NT = BP::NT;
     static_assert(!HELP || (!OBS_ONLY && !NOISY), "the draw wave serves the native re-init step");
+    static_assert(FX::native_overlap <= 0 || (!OBS_ONLY && !NOISY), "native_overlap: the native step");
     (void)k;  // read through kargs_late<kHotKargsOff>()
     extern __shared__ __attribute__((aligned(16))) float lds[];
 #if MARLNAV_STAMPS
@@ -242,8 +273,11 @@ __global__ void __launch_bounds__(64 * (A + HELP))
     STAMP(0);
     float *st = lds + BP::ST;
     const int64_t e0 = blk * E;
-    const int ne = (int)((P - e0) < E ? (P - e0) : E);
-    const bool full = ne == E;
+    const int ne = FX::all_full > 0 ? E : (int)((P - e0) < E ? (P - e0) : E);
+    const bool full = FX::all_full < 0 ? ne == E : FX::all_full > 0;
+    const auto has_form = [&] {
+        return FX::has_formation < 0 ? b.formation != nullptr : FX::has_formation > 0;
+    };
 
     // ---- this wave's actions (lane l: agent w of env l) into its own LDS
     // slots by LDS-DMA issued before the block's spans: the wave waits for
@@ -267,7 +301,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
         if (!OBS_ONLY) {
             block_glds<BS::NB[3]>(BS::K[3], A, w, b.step_num + e0, lds + BP::SN, lane);
             block_glds<BS::NB[4]>(BS::K[4], A, w, b.terminates + e0, lds + BP::TM, lane);
-            if (b.formation)
+            if (has_form())
                 block_glds<BS::NB[5]>(BS::K[5], A, w, b.formation, lds + BP::FORM, lane);
         }
     } else if (!hw) {
@@ -283,14 +317,17 @@ __global__ void __launch_bounds__(64 * (A + HELP))
         if (!OBS_ONLY) {
             block_copy(b.step_num + e0, lds + BP::SN, ne, tid, NT);
             block_copy(b.terminates + e0, reinterpret_cast<uint8_t *>(lds + BP::TM), ne, tid, NT);
-            if (b.formation) block_copy(b.formation, lds + BP::FORM, 5 * A + 2, tid, NT);
+            if (has_form()) block_copy(b.formation, lds + BP::FORM, 5 * A + 2, tid, NT);
         }
     }
     const MarlnavParams pr = load_params(K);
-    const bool wt = (pr.flags & kWriteThroughFlag) != 0;  // written-through outputs
+    // written-through outputs
+    const bool wt =
+        FX::write_through < 0 ? (pr.flags & kWriteThroughFlag) != 0 : FX::write_through > 0;
     // native (non-noisy) re-init: waves 1..A-1 take the finished envs while
     // wave 0 runs the per-env phase (below)
-    const bool overlap = !OBS_ONLY && !NOISY && !K->a.b.fresh_states;
+    const bool overlap = FX::native_overlap < 0 ? !OBS_ONLY && !NOISY && !K->a.b.fresh_states
+                                                : FX::native_overlap > 0;
     // (one Philox block per thread at most: O <= A. At A3/O8 the draws go
     // to the finished-env tail instead: three blocks per thread here cost
     // the stage phase more than they save there, 131072x3x8 18.4 -> 19.0 us
@@ -348,13 +385,15 @@ __global__ void __launch_bounds__(64 * (A + HELP))
             int n = 0;
 #pragma unroll
             for (int ww = 0; ww < A; ++ww)
-                if (w == ww) n = b.formation ? BS::after_actions(ww, true) : BS::after_actions(ww, false);
+                if (w == ww) n = has_form() ? BS::after_actions(ww, true) : BS::after_actions(ww, false);
             wait_vmcnt(n);
         }
         float a0 = actw[lane];
         a1 = actw[E + lane];
         STAMPS_S(0);  // (substamps: this wave's actions landed)
-        if (pr.flags & MARLNAV_SCALE_ACTIONS) {  // ActionScaler (utils.py:546-547)
+        // ActionScaler (utils.py:546-547)
+        if (FX::no_action_scale < 0 ? (pr.flags & MARLNAV_SCALE_ACTIONS) != 0
+                                    : FX::no_action_scale == 0) {
             KArgsK *kl = kargs_late<kHotKargsOff>();
             a0 = kl->p.act_scale[0] * a0 + kl->p.act_mean[0];
             a1 = kl->p.act_scale[1] * a1 + kl->p.act_mean[1];
@@ -445,11 +484,13 @@ __global__ void __launch_bounds__(64 * (A + HELP))
         float rowv[D];
         RowOut ro;
         bool unused = true;
-        if (__builtin_expect(fast, 1) && pr.bond_sharpness == 1.0f && pr.max_at_prop_d == 2.0f)
+        if (__builtin_expect(fast, 1) &&
+            (FX::default_bond < 0 ? pr.bond_sharpness == 1.0f && pr.max_at_prop_d == 2.0f
+                                  : FX::default_bond > 0))
             ro = observe_row_own<A, O, !OBS_ONLY, true, true>(st + 5 * A * l, lds + BP::OB + 2 * O * l,
                                                               lds + BP::TG + 2 * l, w, ox, oy, dx,
                                                               dy, rowv, pr, unused);
-        else if (__builtin_expect(fast, 1))
+        else if (FX::default_bond <= 0 && __builtin_expect(fast, 1))
             ro = observe_row_own<A, O, !OBS_ONLY, true>(st + 5 * A * l, lds + BP::OB + 2 * O * l,
                                                         lds + BP::TG + 2 * l, w, ox, oy, dx, dy,
                                                         rowv, pr, unused);
@@ -464,17 +505,31 @@ __global__ void __launch_bounds__(64 * (A + HELP))
         lds_row_write<D>(obs_rows + r * D, rowv);
         if (!OBS_ONLY) red[r] = make_float4(ro.r_miss, ro.r_hit, __uint_as_float(ro.flags), 0.0f);
     }
+    // the output pointers, read again from the kernarg segment: no scalar
+    // register holds them through the observation, where the entry copies
+    // spilled 14 SGPRs to VGPR lanes (65536x3x3 6.55 -> 6.33 us,
+    // profiles/r05_ab_late_ptrs.txt). FX::ptrs_early: the loads issue here,
+    // ahead of the observe barrier, with the counter path's fields (the
+    // wave waits for them with its LDS writes, under the barrier); else
+    // after it.
+    StepPtrs bo;
+    uint64_t *cnt_early = nullptr;
+    int64_t slots_early = 0;
+    if constexpr (FX::ptrs_early) {
+        KArgsK *kl = kargs_late<kHotKargsOff>();
+        bo = load_ptrs(kl);
+        // (in_sgpr: or the loads sink into wave 0's branch behind the barrier)
+        cnt_early = in_sgpr(kl->a.b.counters);
+        slots_early = in_sgpr(kl->a.waves);
+    }
     __syncthreads();
     STAMP(3);
     if (MARLNAV_AB & 16384) return;  // (AB 16384: observed, then exit)
-    // the output pointers, read again from the kernarg segment here: no
-    // scalar register holds them through the observation, where the entry
-    // copies spilled 14 SGPRs to VGPR lanes (65536x3x3 6.55 -> 6.33 us,
-    // profiles/r05_ab_late_ptrs.txt)
-    const StepPtrs bo = load_ptrs(kargs_late<kHotKargsOff>());
+    if constexpr (!FX::ptrs_early) bo = load_ptrs(kargs_late<kHotKargsOff>());
     float *gobs = in_sgpr(bo.obs + e0 * (A * D));
     if (OBS_ONLY) block_store(gobs, obs_rows, nrow * D, tid, NT, wt);
-    const bool norm = !OBS_ONLY && (pr.flags & MARLNAV_WRITE_OBS_NORM);
+    const bool norm = !OBS_ONLY && (FX::no_norm < 0 ? (pr.flags & MARLNAV_WRITE_OBS_NORM) != 0
+                                                    : FX::no_norm == 0);
     // kBlockEarlyOut: a block with no finished env streams its rows and
     // states from waves 1..A-1 under wave 0's per-env phase (they have
     // nothing else to do there; blocks with finished envs keep the stores
@@ -582,11 +637,18 @@ __global__ void __launch_bounds__(64 * (A + HELP))
             if (lane == 0) {
                 flg[0] = (int)__popcll(finmask);
                 if (c_trunc | c_col | c_tar) {
-                    KArgsK *kl = kargs_late<kHotKargsOff>();
-                    uint64_t *cnt = kl->a.b.counters;
-                    const int64_t slots = kl->a.waves;
-                    if (cnt) {
-                        const int64_t sl = blk < slots ? blk : blk % slots;
+                    uint64_t *cnt = cnt_early;
+                    int64_t slots = slots_early;
+                    if constexpr (!FX::ptrs_early) {
+                        KArgsK *kl = kargs_late<kHotKargsOff>();
+                        cnt = kl->a.b.counters;
+                        slots = kl->a.waves;
+                    }
+                    // (has_counters: a buffer, and a slot for every block)
+                    if (FX::has_counters < 0 ? cnt != nullptr : FX::has_counters > 0) {
+                        const int64_t sl = (FX::has_counters < 0 ? blk < slots : FX::has_counters > 0)
+                                               ? blk
+                                               : blk % slots;
                         if (c_trunc) atomicAdd((unsigned long long *)&cnt[0 * slots + sl], (unsigned long long)c_trunc);
                         if (c_col) atomicAdd((unsigned long long *)&cnt[1 * slots + sl], (unsigned long long)c_col);
                         if (c_tar) atomicAdd((unsigned long long *)&cnt[2 * slots + sl], (unsigned long long)c_tar);

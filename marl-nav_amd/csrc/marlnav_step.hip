@@ -371,6 +371,10 @@ struct BlockVariant {
     size_t lds;
     BlockFn step_draw;  // (or null) the step with a draw wave: grids of at most one block per CU
     int E;              // envs per block
+    // (or null) the step with the launch-invariant choices compiled in
+    // (BlockFixed<wt>, kernel_block.h), [wt]: plain / written-through
+    // outputs; and its draw-wave twin
+    BlockFn step_fixed[2], step_fixed_draw[2];
 };
 
 // compute units of the current device (the draw-wave rule: at most one
@@ -400,17 +404,34 @@ constexpr BlockFn block_draw_fn()
     else return nullptr;
 }
 
+template <int A, int O, bool WT>
+constexpr BlockFn block_fixed_draw_fn()
+{
+    if constexpr (O <= 3) return block_kernel<A, O, false, false, true, BlockFixed<WT>>;
+    else return nullptr;
+}
+
 #define MARLNAV_BLOCK_VARIANT(A, O)                                                    \
     {A, O, block_kernel<A, O, false, false>, block_kernel<A, O, true, false>,          \
      block_kernel<A, O, false, true>, (size_t)BlockPlan<A, O>::FLOATS * 4,             \
-     block_draw_fn<A, O>(), BlockPlan<A, O>::E}
+     block_draw_fn<A, O>(), BlockPlan<A, O>::E, {nullptr, nullptr}, {nullptr, nullptr}}
+// ... and with the BlockFixed instantiations: the shapes the env-block family
+// serves at headline (65536x3x3) and configs[4] (131072x3x8) sizes
+#define MARLNAV_BLOCK_VARIANT_FIXED(A, O)                                              \
+    {A, O, block_kernel<A, O, false, false>, block_kernel<A, O, true, false>,          \
+     block_kernel<A, O, false, true>, (size_t)BlockPlan<A, O>::FLOATS * 4,             \
+     block_draw_fn<A, O>(), BlockPlan<A, O>::E,                                        \
+     {block_kernel<A, O, false, false, false, BlockFixed<false>>,                      \
+      block_kernel<A, O, false, false, false, BlockFixed<true>>},                      \
+     {block_fixed_draw_fn<A, O, false>(), block_fixed_draw_fn<A, O, true>()}}
 const BlockVariant kBlockVariants[] = {
-    MARLNAV_BLOCK_VARIANT(3, 3),
-    MARLNAV_BLOCK_VARIANT(3, 8),
+    MARLNAV_BLOCK_VARIANT_FIXED(3, 3),
+    MARLNAV_BLOCK_VARIANT_FIXED(3, 8),
     MARLNAV_BLOCK_VARIANT(3, 1),
     MARLNAV_BLOCK_VARIANT(2, 1),
 };
 #undef MARLNAV_BLOCK_VARIANT
+#undef MARLNAV_BLOCK_VARIANT_FIXED
 
 const BlockVariant *select_block(const MarlnavDims *d, const MarlnavStepBuffers &b, bool obs_only)
 {
@@ -505,6 +526,25 @@ bool family_allowed(int f)
     return g == MARLNAV_FAMILY_AUTO || g == f;
 }
 
+// marlnav_debug_force_block_traits / marlnav_debug_last_block_traits (the
+// same kind of hook for the env-block step's BlockFixed instantiations)
+std::atomic<int> g_block_traits{MARLNAV_BLOCK_TRAITS_AUTO};
+thread_local int g_last_block_traits = MARLNAV_BLOCK_RAN_GENERAL;
+
+// The BlockFixed selection rule (kernel_block.h): everything its pack
+// compiles in, checked here once per launch. `pr` carries the internal flag
+// bits; L.waves is the counter slot count the kernel indexes by block.
+bool block_fixed_eligible(const MarlnavDims *d, const MarlnavParams &pr,
+                          const MarlnavStepBuffers &b, const BlockVariant &v, const Launch &L,
+                          bool noisy)
+{
+    const int64_t nblk = (d->num_parallel + v.E - 1) / v.E;
+    return d->num_parallel % v.E == 0 && !noisy && !b.fresh_states && b.formation &&
+           !(pr.flags & (MARLNAV_WRITE_OBS_NORM | MARLNAV_SCALE_ACTIONS)) &&
+           pr.bond_sharpness == 1.0f && pr.max_at_prop_d == 2.0f && b.counters &&
+           nblk <= L.waves;
+}
+
 }  // namespace
 
 extern "C" {
@@ -521,6 +561,17 @@ int marlnav_debug_force_family(int family)
 }
 
 int marlnav_debug_last_family(void) { return g_last_family; }
+
+int marlnav_debug_force_block_traits(int mode)
+{
+    const int prev = g_block_traits.load(std::memory_order_relaxed);
+    if (mode < MARLNAV_BLOCK_TRAITS_AUTO || mode > MARLNAV_BLOCK_TRAITS_FIXED_NO_DRAW)
+        return fail(MARLNAV_EINVAL, "unknown block traits mode %d", mode);
+    g_block_traits.store(mode, std::memory_order_relaxed);
+    return prev;
+}
+
+int marlnav_debug_last_block_traits(void) { return g_last_block_traits; }
 
 #if MARLNAV_STAMPS
 int marlnav_debug_stamps(void *buf)
@@ -620,6 +671,7 @@ int marlnav_step(const MarlnavDims *d, const MarlnavParams *pr_in, const Marlnav
             return fail(MARLNAV_EINVAL, "states_out overlaps states");
     }
     const bool noisy = !b->fresh_states && (pr->flags & MARLNAV_NOISY_AGENTS);
+    g_last_block_traits = MARLNAV_BLOCK_RAN_GENERAL;
     const bool fsplit = g_family.load(std::memory_order_relaxed) == MARLNAV_FAMILY_SPLIT;
     if (family_allowed(MARLNAV_FAMILY_SPLIT))
         if (const SplitVariant *v = select_split(d, args.b, false, fsplit)) {
@@ -633,6 +685,21 @@ int marlnav_step(const MarlnavDims *d, const MarlnavParams *pr_in, const Marlnav
             g_last_family = MARLNAV_FAMILY_BLOCK;
             // one block per CU (MI355X: 256 CUs) leaves a SIMD of each CU idle
             const int64_t nblk = (d->num_parallel + v->E - 1) / v->E;
+            const int tmode = g_block_traits.load(std::memory_order_relaxed);
+            const bool draw = !noisy && v->step_draw && nblk <= device_cus() && !b->fresh_states &&
+                              tmode != MARLNAV_BLOCK_TRAITS_FIXED_NO_DRAW;
+            const int wt = (pr->flags & kWriteThroughFlag) != 0;
+            // the launch-invariant choices compiled in, where they all hold
+            if (tmode != MARLNAV_BLOCK_TRAITS_GENERAL && v->step_fixed[wt] &&
+                block_fixed_eligible(d, *pr, args.b, *v, L, noisy)) {
+                if (draw && v->step_fixed_draw[wt]) {
+                    g_last_block_traits = MARLNAV_BLOCK_RAN_FIXED_DRAW;
+                    return launch_block(*v, v->step_fixed_draw[wt], args, *pr, stream,
+                                        "marlnav_step", v->A + 1);
+                }
+                g_last_block_traits = MARLNAV_BLOCK_RAN_FIXED;
+                return launch_block(*v, v->step_fixed[wt], args, *pr, stream, "marlnav_step");
+            }
             if (!noisy && v->step_draw && nblk <= device_cus() && !b->fresh_states)
                 return launch_block(*v, v->step_draw, args, *pr, stream, "marlnav_step", v->A + 1);
             return launch_block(*v, noisy ? v->noisy : v->step, args, *pr, stream, "marlnav_step");
