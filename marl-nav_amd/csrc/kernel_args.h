@@ -121,6 +121,34 @@ __device__ __forceinline__ void glds_span(const void *src, float *dst, unsigned 
     }
 }
 
+// One 8-byte global load per lane into a register pair, outside the
+// compiler's own wait counting: it returns in issue order with the wave's
+// LDS-DMA loads, so the wave waits for it with a counted wait_vmcnt (the
+// LDS-DMA instructions issued after it) and vm_landed(), where a plain load's first use
+// would make the compiler wait vmcnt(0) for every LDS-DMA load in flight.
+// Obligation: between this load and vm_landed() the compiler believes the
+// pair already holds its value, so it must neither copy nor spill it there
+// (a copy would read the registers before the data arrived). It has no
+// reason to - the pair is defined by the asm and next used by vm_landed() -
+// and today no instantiation does; after a compiler or flag change re-check
+// `make asm`: in every block_kernel, no instruction between
+// global_load_dwordx2 v[N:N+1] and the s_waitcnt vmcnt(n) switch may name vN
+// or vN+1. tests/test_block_stage_gpu.py fails on stale actions.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 global_load_x2_raw(const float *p)
+{
+    f32x2 v;
+    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
+    return v;
+}
+
+// after the wait: every later use of v is ordered behind it
+__device__ __forceinline__ f32x2 vm_landed(f32x2 v)
+{
+    asm volatile("" : "+v"(v)::"memory");
+    return v;
+}
+
 // s_waitcnt vmcnt(n) for a wave-uniform n (0..7; larger waits for all)
 __device__ __forceinline__ void wait_vmcnt(int n)
 {

@@ -64,7 +64,7 @@ struct BlockSpans {
     static constexpr int K[N] = {0, 1, 4, 2, 5, 7};
     static constexpr int NB[N] = {BP::R * 20, BP::E * O * 8, BP::E * 8, BP::E * 4, BP::E,
                                   (5 * A + 2) * 4};
-    // LDS-DMA instructions wave w issues after its two action loads (the
+    // LDS-DMA instructions wave w issues after its action load(s) (the
     // formation span counted only when `formation`)
     static constexpr int after_actions(int w, bool formation)
     {
@@ -74,6 +74,48 @@ struct BlockSpans {
         return n;
     }
 };
+
+// The issue sites of a full block's spans in their per-wave form: wave W's
+// spans (BlockSpans: K[i] % A == W) in table order, behind one test of the
+// wave index, instead of one wave test per span (block_glds).
+template <int A, int O, bool OBS_ONLY, int W>
+__device__ __forceinline__ void block_stage_wave(const StepPtrs &b, int64_t e0, float *lds,
+                                                 unsigned lane, bool formation)
+{
+    using BP = BlockPlan<A, O>;
+    using BS = BlockSpans<A, O>;
+    if constexpr (BS::K[0] % A == W)
+        glds_span<BS::NB[0]>(b.states + e0 * (A * 5), lds + BP::ST, lane);
+    if constexpr (BS::K[1] % A == W)
+        glds_span<BS::NB[1]>(b.obstacles + e0 * (O * 2), lds + BP::OB, lane);
+    if constexpr (BS::K[2] % A == W) glds_span<BS::NB[2]>(b.target + e0 * 2, lds + BP::TG, lane);
+    if constexpr (!OBS_ONLY) {
+        if constexpr (BS::K[3] % A == W) glds_span<BS::NB[3]>(b.step_num + e0, lds + BP::SN, lane);
+        if constexpr (BS::K[4] % A == W) glds_span<BS::NB[4]>(b.terminates + e0, lds + BP::TM, lane);
+        if constexpr (BS::K[5] % A == W)
+            if (formation) glds_span<BS::NB[5]>(b.formation, lds + BP::FORM, lane);
+    }
+}
+
+// w: the wave (uniform; the draw wave, w == A, issues nothing)
+template <int A, int O, bool OBS_ONLY, int... W>
+__device__ __forceinline__ void block_stage_waves(std::integer_sequence<int, W...>, int w,
+                                                  const StepPtrs &b, int64_t e0, float *lds,
+                                                  unsigned lane, bool formation)
+{
+    ((w == W ? block_stage_wave<A, O, OBS_ONLY, W>(b, e0, lds, lane, formation) : (void)0), ...);
+}
+
+// How a full block stages. true: every wave loads its own actions, lane l
+// the (angle, accel) pair of agent w of env l, by one 8-byte register load
+// (global_load_x2_raw, kernel_args.h) that feeds the sin/cos from registers,
+// and issues its spans behind one branch on the wave index
+// (block_stage_waves). false: two dword LDS-DMA action loads into the wave's
+// ACTW slots, two LDS reads, and one wave test per span (block_glds). The
+// measurements behind the choice per shape: profiles/stage_pieces_ab.txt,
+// DESIGN.md section 8.
+template <int A, int O>
+constexpr bool kBlockWaveStage = O < 8;
 
 // plain strided copy of n elements by the block's NT threads (partial block)
 template <class T>
@@ -271,6 +313,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
     const int64_t blk = blockIdx.x;
     const int64_t gw = blk * (A + HELP) + w;  // stamps slot
     STAMP(0);
+    STAMP_ISSUED_DECL;
     float *st = lds + BP::ST;
     const int64_t e0 = blk * E;
     const int ne = FX::all_full > 0 ? E : (int)((P - e0) < E ? (P - e0) : E);
@@ -279,22 +322,33 @@ __global__ void __launch_bounds__(64 * (A + HELP))
         return FX::has_formation < 0 ? b.formation != nullptr : FX::has_formation > 0;
     };
 
-    // ---- this wave's actions (lane l: agent w of env l) into its own LDS
-    // slots by LDS-DMA issued before the block's spans: the wave waits for
-    // them alone (vmcnt = the span instructions it issued after them) and
-    // evaluates the heading's sin/cos while the spans are still in flight,
-    // not after the stage barrier
+    // ---- this wave's actions (lane l: agent w of env l), issued before the
+    // block's spans - one register load (kBlockWaveStage), or LDS-DMA into
+    // the wave's own LDS slots: the wave waits for them alone (vmcnt = the
+    // span instructions it issued after them) and evaluates the heading's
+    // sin/cos while the spans are still in flight, not after the stage
+    // barrier
+    constexpr bool WS = kBlockWaveStage<A, O>;
     float *actw = lds + BP::ACTW + 2 * E * (hw ? 0 : w);  // x at [l], y at [E + l]
+    f32x2 act_own = {0.0f, 0.0f};
     if (!OBS_ONLY && full && !hw) {
         const float *pa = h_actions + ((e0 + lane) * A + w) * 2;
-        __builtin_amdgcn_global_load_lds(pa, (LdsVoid *)actw, 4, 0, 0);
-        __builtin_amdgcn_global_load_lds(pa + 1, (LdsVoid *)(actw + E), 4, 0, 0);
+        if constexpr (WS) {
+            act_own = global_load_x2_raw(pa);
+        } else {
+            __builtin_amdgcn_global_load_lds(pa, (LdsVoid *)actw, 4, 0, 0);
+            __builtin_amdgcn_global_load_lds(pa + 1, (LdsVoid *)(actw + E), 4, 0, 0);
+        }
     }
-    // ---- stage the block (spans spread over the waves: span k by wave k % A)
+    // ---- stage the block (spans spread over the waves: span k by wave k % A;
+    // kBlockWaveStage: wave by wave)
     static_assert(BS::NB[0] == R * 20 && BS::NB[1] == E * O * 8 && BS::NB[2] == E * 8 &&
                       BS::NB[3] == E * 4 && BS::NB[4] == E && BS::NB[5] == (5 * A + 2) * 4,
                   "span table and LDS plan agree");
-    if (full) {
+    if (WS && full) {
+        block_stage_waves<A, O, OBS_ONLY>(std::make_integer_sequence<int, A>{}, w, b, e0, lds, lane,
+                                          has_form());
+    } else if (full) {
         block_glds<BS::NB[0]>(BS::K[0], A, w, b.states + e0 * (A * 5), st, lane);
         block_glds<BS::NB[1]>(BS::K[1], A, w, b.obstacles + e0 * (O * 2), lds + BP::OB, lane);
         block_glds<BS::NB[2]>(BS::K[2], A, w, b.target + e0 * 2, lds + BP::TG, lane);
@@ -320,6 +374,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
             if (has_form()) block_copy(b.formation, lds + BP::FORM, 5 * A + 2, tid, NT);
         }
     }
+    STAMP_ISSUED();  // (substamps 2: this wave's last staging load issued)
     const MarlnavParams pr = load_params(K);
     // written-through outputs
     const bool wt =
@@ -380,7 +435,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
     float sn = 0.0f, c = 1.0f, a1 = 0.0f;
     if (!OBS_ONLY && !hw) {
         if (full) {
-            // span instructions this wave issued after its two action loads
+            // span instructions this wave issued after its action load(s)
             // (BlockSpans: the same table as the issue sites above)
             int n = 0;
 #pragma unroll
@@ -388,8 +443,15 @@ __global__ void __launch_bounds__(64 * (A + HELP))
                 if (w == ww) n = has_form() ? BS::after_actions(ww, true) : BS::after_actions(ww, false);
             wait_vmcnt(n);
         }
-        float a0 = actw[lane];
-        a1 = actw[E + lane];
+        float a0;
+        if (WS && full) {
+            act_own = vm_landed(act_own);
+            a0 = act_own.x;
+            a1 = act_own.y;
+        } else {
+            a0 = actw[lane];
+            a1 = actw[E + lane];
+        }
         STAMPS_S(0);  // (substamps: this wave's actions landed)
         // ActionScaler (utils.py:546-547)
         if (FX::no_action_scale < 0 ? (pr.flags & MARLNAV_SCALE_ACTIONS) != 0
@@ -778,6 +840,7 @@ __global__ void __launch_bounds__(64 * (A + HELP))
 #if MARLNAV_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     STAMP(7);
+    STAMP_ISSUED_STORE();
     if (lane == 0) {
         *STAMP_PTR((size_t)gw * 24 + 16) = t_entry;
         *STAMP_PTR((size_t)gw * 24 + 17) = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));

@@ -37,7 +37,26 @@ typedef __attribute__((address_space(1))) unsigned long long stamp_t;
 #define STAMPX(k) \
     do {          \
     } while (0)
+// MARLNAV_SUBSTAMPS=2: slot 23 is "this wave's last staging load issued"
+// (STAMP_ISSUED) instead of "row computed" (STAMPS_S(3)). The time is held
+// in SGPRs and stored with the end-of-kernel stamps: a store at the issue
+// point would be a VMEM operation younger than the wave's own action load,
+// and the counted vmcnt wait that follows could then return before the load.
+#if MARLNAV_SUBSTAMPS == 2
+#define STAMPS_S(k)                       \
+    do {                                  \
+        if ((k) != 3) STAMP_SLOT_(k);     \
+    } while (0)
+#define STAMP_ISSUED_DECL unsigned long long t_issued = 0
+#define STAMP_ISSUED() \
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_issued)::"memory")
+#define STAMP_ISSUED_STORE()                                           \
+    do {                                                               \
+        if (lane == 0) *STAMP_PTR((size_t)gw * 24 + 23) = t_issued;    \
+    } while (0)
+#else
 #define STAMPS_S(k) STAMP_SLOT_(k)
+#endif
 #else
 #define STAMPX(k) STAMP_SLOT_(k)
 #define STAMPS_S(k) \
@@ -53,6 +72,17 @@ typedef __attribute__((address_space(1))) unsigned long long stamp_t;
     } while (0)
 #define STAMP(k) \
     do {         \
+    } while (0)
+#endif
+#ifndef STAMP_ISSUED
+#define STAMP_ISSUED_DECL \
+    do {                  \
+    } while (0)
+#define STAMP_ISSUED() \
+    do {               \
+    } while (0)
+#define STAMP_ISSUED_STORE() \
+    do {                     \
     } while (0)
 #endif
 

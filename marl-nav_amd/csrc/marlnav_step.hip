@@ -34,6 +34,8 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <type_traits>
+#include <utility>
 
 #include <stdarg.h>
 #include <stdint.h>
