@@ -1,10 +1,14 @@
 // host_util.h - what the host side of every entry point outside the step
 // kernels shares: the formatted failure, the launch status, the overlap test,
 // the failure of one step of a chained call and the policy shape check.
-// Included inside each translation unit's anonymous namespace, after
-// <stdarg.h>, <stdio.h>, marlnav.h and the declaration of
-// marlnav_internal_fail.
+// Included at file scope, after <stdarg.h>, <stdio.h> and marlnav.h; what it
+// defines lives in the translation unit's anonymous namespace.
 #pragma once
+
+// marlnav_step.hip: stores the message for marlnav_last_error, returns code
+__attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const char *msg);
+
+namespace {
 
 #include "policy_limits.h"
 
@@ -59,3 +63,5 @@ int check_policy_shape(const char *who, int64_t P, int A, int D, int H)
                      "[1, %d]", who, D, A, kMaxObstP);
     return 0;
 }
+
+}  // namespace

@@ -58,12 +58,11 @@
 
 #include "../../include/marlnav.h"
 #include "adam_element.h"
-
-__attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const char *msg);
+#include "host_util.h"
+#include "ppo_update.h"
 
 namespace {
 
-#include "host_util.h"
 #include "device_rng.h"  // Philox2x32-10 and the key mixing, for the minibatch permutations
 
 constexpr int kThreads = 256;
@@ -320,13 +319,6 @@ int64_t table_blocks(const MarlnavAdamDims *d)
     return (items + kThreads - 1) / kThreads;
 }
 
-// the clipped step's own arguments; norm_out is the call's norm_out / norm_log
-struct ClipArgs {
-    double max_norm;
-    double *norm_work;
-    double *norm_out;  // of the next step; NULL: not recorded
-};
-
 int check_clip(double max_norm, const void *norm_work, const void *norm_out, const char *out_name)
 {
     if (!(max_norm > 0.0))  // a NaN is not greater
@@ -401,25 +393,41 @@ int enqueue_adam(const MarlnavAdamDims *d, const MarlnavAdamBuffers *b, hipStrea
     return launch_status();
 }
 
-// The Adam table of an update call must be the network's own: slot i is the
-// i-th weight of `w`, its grad_ pointer and its size.
-int check_table(const char *net, int count, const float *const *w, float *const *gw,
-                const int64_t *size, const char *const *name, const MarlnavAdamDims *ad,
-                const MarlnavAdamBuffers *ab)
+// The Adam table of an update or phase call must be the network's own: slot i
+// is the network's i-th weight, its grad_ pointer and its size.
+int check_table(int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab)
 {
+    struct Slot {
+        const float *w;
+        float *gw;
+        int64_t size;
+        const char *name;
+    };
+#define SLOT(field, size) {b->field, b->grad_##field, size, #field}
+    const int64_t H = d->hidden_size, D = d->obs_dim, AD = (int64_t)d->num_agents * D;
+    const Slot actor[6] = {SLOT(actor_fc1_w, H * D), SLOT(actor_fc1_b, H),
+                           SLOT(actor_mu_w, 2 * H),  SLOT(actor_mu_b, 2),
+                           SLOT(actor_std_w, 2 * H), SLOT(actor_std_b, 2)};
+    const Slot critic[4] = {SLOT(critic_fc1_w, H * AD), SLOT(critic_fc1_b, H),
+                            SLOT(critic_fc2_w, H), SLOT(critic_fc2_b, 1)};
+#undef SLOT
+    const bool is_actor = network == MARLNAV_NETWORK_ACTOR;
+    const Slot *slot = is_actor ? actor : critic;
+    const int count = is_actor ? 6 : 4;
     if (ad->num_tensors != count)
         return failf(MARLNAV_EINVAL, "adam table: num_tensors=%d, the %s has %d parameters",
-                     ad->num_tensors, net, count);
+                     ad->num_tensors, is_actor ? "actor" : "critic", count);
     for (int i = 0; i < count; ++i) {
-        if (ab->param[i] != w[i])
+        if (ab->param[i] != slot[i].w)
             return failf(MARLNAV_EINVAL, "adam table: param[%d] is not the ppo buffer %s", i,
-                         name[i]);
-        if (ab->grad[i] != gw[i])
+                         slot[i].name);
+        if (ab->grad[i] != slot[i].gw)
             return failf(MARLNAV_EINVAL, "adam table: grad[%d] is not the ppo buffer grad_%s", i,
-                         name[i]);
-        if (ad->numel[i] != size[i])
+                         slot[i].name);
+        if (ad->numel[i] != slot[i].size)
             return failf(MARLNAV_EINVAL, "adam table: numel[%d]=%lld, %s has %lld elements", i,
-                         (long long)ad->numel[i], name[i], (long long)size[i]);
+                         (long long)ad->numel[i], slot[i].name, (long long)slot[i].size);
     }
     return 0;
 }
@@ -457,56 +465,53 @@ extern "C" int marlnav_adam_step_clipped(const MarlnavAdamDims *d, const Marlnav
 
 namespace {
 
-// clip NULL: marlnav_ppo_actor_update_mode; given: its _clipped form
-int actor_update(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
-                 double ent_const, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
-                 int advantage_mode, const ClipArgs *clip, void *stream)
+// the update's gradient launches and, where they leave it owed, its Adam step
+// (gated by the stop where the update is monitored); checked arguments only
+int enqueue_update(const PpoUpdate &u, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                   hipStream_t s)
 {
-    // every check of both halves before the first launch: the ppo dims
-    // (marlnav_ppo_work_size runs them), the Adam arguments, the table; the
-    // gradient call then checks its own buffers before it launches
-    if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
-    if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
-    int rc = check_adam(ad, ab);
-    if (rc) return rc;
-    const int64_t H = d->hidden_size, D = d->obs_dim;
-    const float *const w[6] = {b->actor_fc1_w, b->actor_fc1_b, b->actor_mu_w,
-                               b->actor_mu_b,  b->actor_std_w, b->actor_std_b};
-    float *const gw[6] = {b->grad_actor_fc1_w, b->grad_actor_fc1_b, b->grad_actor_mu_w,
-                          b->grad_actor_mu_b,  b->grad_actor_std_w, b->grad_actor_std_b};
-    const int64_t size[6] = {H * D, H, 2 * H, 2, 2 * H, 2};
-    const char *const name[6] = {"actor_fc1_w", "actor_fc1_b", "actor_mu_w",
-                                 "actor_mu_b",  "actor_std_w", "actor_std_b"};
-    rc = check_table("actor", 6, w, gw, size, name, ad, ab);
-    if (rc) return rc;
-    if (clip) rc = check_clip(clip->max_norm, clip->norm_work, clip->norm_out, "norm_out");
-    if (rc) return rc;
-    rc = marlnav_ppo_actor_grad_mode(d, b, epsilon, ent_const, advantage_mode, stream);
-    if (rc) return rc;
-    return enqueue_adam(ad, ab, (hipStream_t)stream, clip);
+    bool adam_owed;
+    const int rc = marlnav_internal_ppo_enqueue(&u, d, b, s, &adam_owed);
+    if (rc || !adam_owed) return rc;
+    return enqueue_adam(u.ad, u.ab, s, u.clip, u.diag_row ? u.stop : nullptr);
 }
 
-int critic_update(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
-                  const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, const ClipArgs *clip,
-                  void *stream)
+// a single-update entry's update: never folded, so the plain gradient
+// launches, then the Adam step in launches of its own (clip NULL:
+// marlnav_adam_step's; given: the clipped step's)
+PpoUpdate single_update(int network, double epsilon, double ent_const, int advantage_mode,
+                        const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
+                        const ClipArgs *clip)
 {
+    PpoUpdate u = {};
+    u.network = network;
+    u.epsilon = epsilon;
+    u.ent_const = ent_const;
+    u.advantage_mode = advantage_mode;
+    u.ad = ad;
+    u.ab = ab;
+    u.clip = clip;
+    return u;
+}
+
+int run_update(const PpoUpdate &u, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+               void *stream)
+{
+    // every check of both halves before the first launch: the ppo dims
+    // (marlnav_ppo_work_size runs them), the Adam arguments, the table, the
+    // clip, then what the gradient call checks
     if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
     if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
-    int rc = check_adam(ad, ab);
+    int rc = check_adam(u.ad, u.ab);
     if (rc) return rc;
-    const int64_t H = d->hidden_size, AD = (int64_t)d->num_agents * d->obs_dim;
-    const float *const w[4] = {b->critic_fc1_w, b->critic_fc1_b, b->critic_fc2_w, b->critic_fc2_b};
-    float *const gw[4] = {b->grad_critic_fc1_w, b->grad_critic_fc1_b, b->grad_critic_fc2_w,
-                          b->grad_critic_fc2_b};
-    const int64_t size[4] = {H * AD, H, H, 1};
-    const char *const name[4] = {"critic_fc1_w", "critic_fc1_b", "critic_fc2_w", "critic_fc2_b"};
-    rc = check_table("critic", 4, w, gw, size, name, ad, ab);
+    rc = check_table(u.network, d, b, u.ad, u.ab);
     if (rc) return rc;
-    if (clip) rc = check_clip(clip->max_norm, clip->norm_work, clip->norm_out, "norm_out");
+    if (u.clip)
+        rc = check_clip(u.clip->max_norm, u.clip->norm_work, u.clip->norm_out, "norm_out");
     if (rc) return rc;
-    rc = marlnav_ppo_critic_grad(d, b, epsilon, stream);
+    rc = marlnav_internal_ppo_validate(u.network, u.advantage_mode, d, b);
     if (rc) return rc;
-    return enqueue_adam(ad, ab, (hipStream_t)stream, clip);
+    return enqueue_update(u, d, b, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -517,7 +522,8 @@ extern "C" int marlnav_ppo_actor_update_mode(const MarlnavPpoDims *d, const Marl
                                              const MarlnavAdamBuffers *ab, int advantage_mode,
                                              void *stream)
 {
-    return actor_update(d, b, epsilon, ent_const, ad, ab, advantage_mode, nullptr, stream);
+    return run_update(single_update(MARLNAV_NETWORK_ACTOR, epsilon, ent_const, advantage_mode, ad,
+                                    ab, nullptr), d, b, stream);
 }
 
 extern "C" int marlnav_ppo_actor_update_clipped(const MarlnavPpoDims *d,
@@ -528,7 +534,8 @@ extern "C" int marlnav_ppo_actor_update_clipped(const MarlnavPpoDims *d,
                                                 double *norm_out, void *stream)
 {
     const ClipArgs clip = {max_norm, norm_work, norm_out};
-    return actor_update(d, b, epsilon, ent_const, ad, ab, advantage_mode, &clip, stream);
+    return run_update(single_update(MARLNAV_NETWORK_ACTOR, epsilon, ent_const, advantage_mode, ad,
+                                    ab, &clip), d, b, stream);
 }
 
 extern "C" int marlnav_ppo_actor_update(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
@@ -544,7 +551,8 @@ extern "C" int marlnav_ppo_critic_update(const MarlnavPpoDims *d, const MarlnavP
                                          double epsilon, const MarlnavAdamDims *ad,
                                          const MarlnavAdamBuffers *ab, void *stream)
 {
-    return critic_update(d, b, epsilon, ad, ab, nullptr, stream);
+    return run_update(single_update(MARLNAV_NETWORK_CRITIC, epsilon, 0.0,
+                                    MARLNAV_ADVANTAGE_REFERENCE, ad, ab, nullptr), d, b, stream);
 }
 
 extern "C" int marlnav_ppo_critic_update_clipped(const MarlnavPpoDims *d,
@@ -555,315 +563,13 @@ extern "C" int marlnav_ppo_critic_update_clipped(const MarlnavPpoDims *d,
                                                  void *stream)
 {
     const ClipArgs clip = {max_norm, norm_work, norm_out};
-    return critic_update(d, b, epsilon, ad, ab, &clip, stream);
+    return run_update(single_update(MARLNAV_NETWORK_CRITIC, epsilon, 0.0,
+                                    MARLNAV_ADVANTAGE_REFERENCE, ad, ab, &clip), d, b, stream);
 }
 
 // =========================================================================
-// one whole train_actor / train_critic as one call
+// the minibatch permutations of the shuffled phase
 // =========================================================================
-__attribute__((visibility("hidden"))) int marlnav_internal_ppo_fold(
-    int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
-    double ent_const, int advantage_mode, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
-    void *stream, int check_only);
-__attribute__((visibility("hidden"))) int marlnav_internal_ppo_actor_clip_fold(
-    const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon, double ent_const,
-    int advantage_mode, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, double max_norm,
-    double *norm_out, void *stream);
-
-namespace {
-
-// whether the clipped phase folds the actor's clip and Adam step into
-// actor_finish (marlnav_debug_clip_fold; the default is the measured decision
-// of DESIGN.md §16)
-int g_clip_fold = MARLNAV_CLIP_FOLD_DEFAULT;
-
-// the (lo, hi) list against the buffer's steps
-int check_bounds(const MarlnavPpoDims *d, const int64_t *bounds, int64_t num_batches)
-{
-    if (num_batches < 1)
-        return failf(MARLNAV_EINVAL, "train: num_batches=%lld < 1", (long long)num_batches);
-    if (!bounds) return marlnav_internal_fail(MARLNAV_EINVAL, "train: bounds is NULL");
-    for (int64_t j = 0; j < num_batches; ++j) {
-        const int64_t lo = bounds[2 * j], hi = bounds[2 * j + 1];
-        if (lo < 0 || hi <= lo || hi > d->num_steps)
-            return failf(MARLNAV_EINVAL,
-                         "train: bounds[%lld]=(%lld, %lld) is not a non-empty range of the %lld "
-                         "steps", (long long)j, (long long)lo, (long long)hi,
-                         (long long)d->num_steps);
-    }
-    return 0;
-}
-
-// the structs of minibatch (lo, hi): dims of hi - lo steps, data pointers at step lo
-void minibatch(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, int64_t lo, int64_t hi,
-               double *loss, MarlnavPpoDims *md, MarlnavPpoBuffers *mb)
-{
-    *md = *d;
-    md->num_steps = hi - lo;
-    *mb = *b;
-    const int64_t rows = lo * d->num_parallel, arows = rows * d->num_agents;
-    mb->obs = b->obs + arows * d->obs_dim;
-    if (b->actions) mb->actions = b->actions + arows * 2;
-    if (b->log_probs) mb->log_probs = b->log_probs + arows;
-    if (b->values) mb->values = b->values + rows;
-    mb->returns = b->returns + rows;
-    mb->loss = loss;
-}
-
-}  // namespace
-
-namespace {
-
-int64_t train_work_size(const MarlnavPpoDims *d, const int64_t *bounds, int64_t num_batches,
-                        int64_t (*one)(const MarlnavPpoDims *))
-{
-    if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
-    const int rc = check_bounds(d, bounds, num_batches);
-    if (rc) return rc;
-    int64_t need = 0;
-    for (int64_t j = 0; j < num_batches; ++j) {
-        MarlnavPpoDims md = *d;
-        md.num_steps = bounds[2 * j + 1] - bounds[2 * j];
-        const int64_t w = one(&md);
-        if (w < 0) return w;
-        if (w > need) need = w;
-    }
-    return need;
-}
-
-}  // namespace
-
-extern "C" int64_t marlnav_ppo_train_work_size(const MarlnavPpoDims *d, const int64_t *bounds,
-                                               int64_t num_batches)
-{
-    return train_work_size(d, bounds, num_batches, marlnav_ppo_work_size);
-}
-
-extern "C" int64_t marlnav_ppo_train_diag_work_size(const MarlnavPpoDims *d,
-                                                    const int64_t *bounds, int64_t num_batches)
-{
-    return train_work_size(d, bounds, num_batches, marlnav_ppo_diag_work_size);
-}
-
-namespace {
-
-// every check of a phase call before its first launch; clip as for train_phase
-int check_train_phase(int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
-                      const int64_t *bounds, int64_t num_batches, int64_t num_epochs,
-                      double epsilon, double ent_const, const MarlnavAdamDims *ad,
-                      const MarlnavAdamBuffers *ab, double *loss_log, int advantage_mode,
-                      const ClipArgs *clip, void *stream)
-{
-    if (network != MARLNAV_NETWORK_ACTOR && network != MARLNAV_NETWORK_CRITIC)
-        return failf(MARLNAV_EINVAL, "train: network=%d must be MARLNAV_NETWORK_ACTOR or _CRITIC", network);
-    if (advantage_mode != MARLNAV_ADVANTAGE_REFERENCE && advantage_mode != MARLNAV_ADVANTAGE_ENV)
-        return failf(MARLNAV_EINVAL, "train: advantage_mode=%d must be MARLNAV_ADVANTAGE_REFERENCE or _ENV",
-                     advantage_mode);
-    // the own-env pairing is the actor's: it reads no values
-    const bool need_values =
-        network == MARLNAV_NETWORK_CRITIC || advantage_mode == MARLNAV_ADVANTAGE_REFERENCE;
-    if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
-    if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
-    if (num_epochs < 1) return failf(MARLNAV_EINVAL, "train: num_epochs=%lld < 1", (long long)num_epochs);
-    int rc = check_bounds(d, bounds, num_batches);
-    if (rc) return rc;
-    if (!loss_log) return marlnav_internal_fail(MARLNAV_EINVAL, "train: loss_log is NULL");
-    if (addr(loss_log) & 7u)
-        return marlnav_internal_fail(MARLNAV_EINVAL, "train: loss_log must be 8-byte aligned");
-    rc = check_adam(ad, ab);
-    if (rc) return rc;
-    const int64_t H = d->hidden_size, D = d->obs_dim, AD = (int64_t)d->num_agents * D;
-    if (network == MARLNAV_NETWORK_ACTOR) {
-        const float *const w[6] = {b->actor_fc1_w, b->actor_fc1_b, b->actor_mu_w,
-                                   b->actor_mu_b,  b->actor_std_w, b->actor_std_b};
-        float *const gw[6] = {b->grad_actor_fc1_w, b->grad_actor_fc1_b, b->grad_actor_mu_w,
-                              b->grad_actor_mu_b,  b->grad_actor_std_w, b->grad_actor_std_b};
-        const int64_t size[6] = {H * D, H, 2 * H, 2, 2 * H, 2};
-        const char *const name[6] = {"actor_fc1_w", "actor_fc1_b", "actor_mu_w",
-                                     "actor_mu_b",  "actor_std_w", "actor_std_b"};
-        rc = check_table("actor", 6, w, gw, size, name, ad, ab);
-    } else {
-        const float *const w[4] = {b->critic_fc1_w, b->critic_fc1_b, b->critic_fc2_w,
-                                   b->critic_fc2_b};
-        float *const gw[4] = {b->grad_critic_fc1_w, b->grad_critic_fc1_b, b->grad_critic_fc2_w,
-                              b->grad_critic_fc2_b};
-        const int64_t size[4] = {H * AD, H, H, 1};
-        const char *const name[4] = {"critic_fc1_w", "critic_fc1_b", "critic_fc2_w",
-                                     "critic_fc2_b"};
-        rc = check_table("critic", 4, w, gw, size, name, ad, ab);
-    }
-    if (rc) return rc;
-    if (clip) rc = check_clip(clip->max_norm, clip->norm_work, clip->norm_out, "norm_log");
-    if (rc) return rc;
-    if (!b->obs) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer obs is NULL");
-    if (need_values && !b->values)
-        return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer values is NULL");
-    if (!b->returns) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer returns is NULL");
-    MarlnavPpoDims md;
-    MarlnavPpoBuffers mb;
-    for (int64_t j = 0; j < num_batches; ++j) {  // dims and buffers of every minibatch
-        minibatch(d, b, bounds[2 * j], bounds[2 * j + 1], loss_log, &md, &mb);
-        rc = marlnav_internal_ppo_fold(network, &md, &mb, epsilon, ent_const, advantage_mode, ad,
-                                       ab, stream, 1);
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-// clip NULL: marlnav_ppo_train_phase_mode; given: its _clipped form, whose
-// norm_out is the norm_log (update k writes [k]) or NULL
-int train_phase(int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
-                const int64_t *bounds, int64_t num_batches, int64_t num_epochs, double epsilon,
-                double ent_const, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
-                double *loss_log, int advantage_mode, const ClipArgs *clip, void *stream)
-{
-    int rc = check_train_phase(network, d, b, bounds, num_batches, num_epochs, epsilon, ent_const,
-                               ad, ab, loss_log, advantage_mode, clip, stream);
-    if (rc) return rc;
-    MarlnavPpoDims md;
-    MarlnavPpoBuffers mb;
-    // ---- num_epochs x num_batches updates, epoch-major: two launches for the
-    // actor, two or three for the critic, each with the Adam step inside (a
-    // large actor keeps the four launches of marlnav_ppo_actor_update)
-    int64_t k = 0;
-    for (int64_t e = 0; e < num_epochs; ++e)
-        for (int64_t j = 0; j < num_batches; ++j, ++k) {
-            minibatch(d, b, bounds[2 * j], bounds[2 * j + 1], loss_log + k, &md, &mb);
-            if (clip) {
-                double *const norm_k = clip->norm_out ? clip->norm_out + k : nullptr;
-                if (network == MARLNAV_NETWORK_ACTOR && g_clip_fold) {
-                    // a small actor: norm, clip and update inside actor_finish
-                    rc = marlnav_internal_ppo_actor_clip_fold(&md, &mb, epsilon, ent_const,
-                                                              advantage_mode, ad, ab,
-                                                              clip->max_norm, norm_k, stream);
-                    if (rc < 0) return rc;
-                    if (rc == 0) continue;
-                }
-                // the folded finish kernels of the unclipped phase update
-                // elements before the norm exists: the gradient launches alone,
-                // then the clipped step
-                rc = network == MARLNAV_NETWORK_ACTOR
-                         ? marlnav_ppo_actor_grad_mode(&md, &mb, epsilon, ent_const,
-                                                       advantage_mode, stream)
-                         : marlnav_ppo_critic_grad(&md, &mb, epsilon, stream);
-                if (rc) return rc;
-                const ClipArgs ck = {clip->max_norm, clip->norm_work, norm_k};
-                rc = enqueue_adam(ad, ab, (hipStream_t)stream, &ck);
-                if (rc) return rc;
-                continue;
-            }
-            rc = marlnav_internal_ppo_fold(network, &md, &mb, epsilon, ent_const, advantage_mode,
-                                           ad, ab, stream, 0);
-            if (rc == 1) rc = enqueue_adam(ad, ab, (hipStream_t)stream);  // not folded
-            if (rc) return rc;
-        }
-    return 0;
-}
-
-}  // namespace
-
-extern "C" int marlnav_ppo_train_phase_mode(int network, const MarlnavPpoDims *d,
-                                            const MarlnavPpoBuffers *b, const int64_t *bounds,
-                                            int64_t num_batches, int64_t num_epochs,
-                                            double epsilon, double ent_const,
-                                            const MarlnavAdamDims *ad,
-                                            const MarlnavAdamBuffers *ab, double *loss_log,
-                                            int advantage_mode, void *stream)
-{
-    return train_phase(network, d, b, bounds, num_batches, num_epochs, epsilon, ent_const, ad, ab,
-                       loss_log, advantage_mode, nullptr, stream);
-}
-
-extern "C" int marlnav_ppo_train_phase_clipped(int network, const MarlnavPpoDims *d,
-                                               const MarlnavPpoBuffers *b, const int64_t *bounds,
-                                               int64_t num_batches, int64_t num_epochs,
-                                               double epsilon, double ent_const,
-                                               const MarlnavAdamDims *ad,
-                                               const MarlnavAdamBuffers *ab, double *loss_log,
-                                               int advantage_mode, double max_norm,
-                                               double *norm_work, double *norm_log, void *stream)
-{
-    const ClipArgs clip = {max_norm, norm_work, norm_log};
-    return train_phase(network, d, b, bounds, num_batches, num_epochs, epsilon, ent_const, ad, ab,
-                       loss_log, advantage_mode, &clip, stream);
-}
-
-extern "C" int marlnav_ppo_train_phase(int network, const MarlnavPpoDims *d,
-                                       const MarlnavPpoBuffers *b, const int64_t *bounds,
-                                       int64_t num_batches, int64_t num_epochs, double epsilon,
-                                       double ent_const, const MarlnavAdamDims *ad,
-                                       const MarlnavAdamBuffers *ab, double *loss_log,
-                                       void *stream)
-{
-    return marlnav_ppo_train_phase_mode(network, d, b, bounds, num_batches, num_epochs, epsilon,
-                                        ent_const, ad, ab, loss_log, MARLNAV_ADVANTAGE_REFERENCE,
-                                        stream);
-}
-
-// =========================================================================
-// the monitored actor phase
-// =========================================================================
-__attribute__((visibility("hidden"))) int marlnav_internal_ppo_actor_diag(
-    const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon, double ent_const,
-    int advantage_mode, double *diag_row, int64_t *stop, double target_kl, int64_t k, void *stream);
-
-extern "C" int marlnav_ppo_train_phase_monitored(
-    int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, const int64_t *bounds,
-    int64_t num_batches, int64_t num_epochs, double epsilon, double ent_const,
-    const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, double *loss_log, int advantage_mode,
-    double max_norm, double *norm_work, double *norm_log, double target_kl, double *diag_log,
-    int64_t *stop, void *stream)
-{
-    // ---- every check before the first launch
-    if (network == MARLNAV_NETWORK_CRITIC)
-        return marlnav_internal_fail(MARLNAV_EINVAL,
-                                     "train: the monitored phase is the actor's; network is "
-                                     "MARLNAV_NETWORK_CRITIC");
-    const bool clipped = max_norm != MARLNAV_MAX_NORM_NONE;  // a NaN is refused by check_clip
-    if (!clipped && (norm_work || norm_log))
-        return marlnav_internal_fail(MARLNAV_EINVAL,
-                                     "clip: norm_work and norm_log must be NULL with "
-                                     "max_norm = MARLNAV_MAX_NORM_NONE");
-    const ClipArgs clip = {max_norm, norm_work, norm_log};
-    int rc = check_train_phase(network, d, b, bounds, num_batches, num_epochs, epsilon, ent_const,
-                               ad, ab, loss_log, advantage_mode, clipped ? &clip : nullptr, stream);
-    if (rc) return rc;
-    if (!(target_kl > 0.0))  // a NaN is not greater
-        return failf(MARLNAV_EINVAL, "train: target_kl=%g must be > 0 (+inf: monitor only)",
-                     target_kl);
-    if (!diag_log) return marlnav_internal_fail(MARLNAV_EINVAL, "train: diag_log is NULL");
-    if (addr(diag_log) & 7u)
-        return marlnav_internal_fail(MARLNAV_EINVAL, "train: diag_log must be 8-byte aligned");
-    if (!stop) return marlnav_internal_fail(MARLNAV_EINVAL, "train: stop is NULL");
-    if (addr(stop) & 7u)
-        return marlnav_internal_fail(MARLNAV_EINVAL, "train: stop must be 8-byte aligned");
-    // ---- num_epochs x num_batches updates: the diagnostic gradient launches,
-    // whose finish publishes the flag, then the gated Adam launches (2, or 3
-    // with a clip). Nothing is folded: an update that stops must not step.
-    MarlnavPpoDims md;
-    MarlnavPpoBuffers mb;
-    int64_t k = 0;
-    for (int64_t e = 0; e < num_epochs; ++e)
-        for (int64_t j = 0; j < num_batches; ++j, ++k) {
-            minibatch(d, b, bounds[2 * j], bounds[2 * j + 1], loss_log + k, &md, &mb);
-            rc = marlnav_internal_ppo_actor_diag(&md, &mb, epsilon, ent_const, advantage_mode,
-                                                 diag_log + MARLNAV_DIAG_ROW * k, stop, target_kl, k, stream);
-            if (rc) return rc;
-            const ClipArgs ck = {max_norm, norm_work, norm_log ? norm_log + k : nullptr};
-            rc = enqueue_adam(ad, ab, (hipStream_t)stream, clipped ? &ck : nullptr, stop);
-            if (rc) return rc;
-        }
-    return 0;
-}
-
-// =========================================================================
-// shuffled minibatches
-// =========================================================================
-__attribute__((visibility("hidden"))) int marlnav_internal_ppo_grad_steps(
-    int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, const int32_t *steps,
-    double epsilon, double ent_const, int advantage_mode, double *diag_row, int64_t *stop,
-    double target_kl, int64_t k, void *stream, int check_only);
-
 namespace {
 
 constexpr int64_t kPermMaxLen = 65535;     // L: a draw's block index stays below 2^15
@@ -941,13 +647,6 @@ void enqueue_permutations(int64_t L, int64_t E, uint64_t seed, int network, uint
                        (int)E, native_seed_mix(seed), (uint32_t)network, counter);
 }
 
-// minibatch j of an epoch: entries [j bs, (j + 1) bs) of its permutation, the
-// last one with the L % bs left over
-inline int64_t shuffled_steps(int64_t L, int64_t bs, int64_t j)
-{
-    return j + 1 < L / bs ? bs : L - j * bs;
-}
-
 }  // namespace
 
 extern "C" int marlnav_minibatch_permutations(int64_t L, int64_t E, uint64_t seed, int network,
@@ -959,24 +658,350 @@ extern "C" int marlnav_minibatch_permutations(int64_t L, int64_t E, uint64_t see
     return launch_status();
 }
 
-extern "C" int64_t marlnav_ppo_train_shuffled_work_size(const MarlnavPpoDims *d,
-                                                        int64_t batch_size, int diag)
+// =========================================================================
+// one whole train_actor / train_critic as one call (clipped
+// §16, monitored §17, shuffled §18)
+// =========================================================================
+namespace {
+
+// what a phase or work-size entry was given
+struct Phase {
+    int network;
+    const MarlnavPpoDims *d;
+    const MarlnavPpoBuffers *b;
+    // the minibatch schedule. Contiguous: minibatch j is steps bounds[2 j] ..
+    // bounds[2 j + 1] - 1. Shuffled: one launch first draws a permutation of
+    // all num_steps steps per epoch into `table`; minibatch j of epoch e is
+    // entries [j batch_size, (j + 1) batch_size) of row e, the last one with
+    // the num_steps % batch_size left over
+    bool shuffled;
+    const int64_t *bounds;
+    int64_t num_batches;
+    int64_t batch_size;
+    uint64_t seed;
+    uint64_t *counter;
+    int32_t *table;
+    int64_t num_epochs;
+    double epsilon, ent_const;
+    int advantage_mode;
+    const MarlnavAdamDims *ad;
+    const MarlnavAdamBuffers *ab;
+    double *loss_log;  // update k writes [k]
+    bool clipped;
+    ClipArgs clip;  // norm_out: the norm_log (update k writes [k]) or NULL
+    bool monitored;
+    double target_kl;
+    double *diag_log;  // update k writes row k
+    int64_t *stop;
+};
+
+inline int64_t num_minibatches(const Phase &p)
 {
-    if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
-    const int64_t L = d->num_steps;
-    if (batch_size < 1 || L / batch_size < 1)
-        return failf(MARLNAV_EINVAL, "shuffle: batch_size=%lld gives no minibatch of %lld steps",
-                     (long long)batch_size, (long long)L);
+    return p.shuffled ? p.d->num_steps / p.batch_size : p.num_batches;
+}
+
+inline int64_t minibatch_steps(const Phase &p, int64_t j)
+{
+    if (!p.shuffled) return p.bounds[2 * j + 1] - p.bounds[2 * j];
+    const int64_t L = p.d->num_steps, bs = p.batch_size;
+    return j + 1 < L / bs ? bs : L - j * bs;
+}
+
+// minibatches [first_size(p), num_minibatches(p)) have every size the schedule
+// has: a shuffled epoch has two
+inline int64_t first_size(const Phase &p)
+{
+    const int64_t B = num_minibatches(p);
+    return p.shuffled && B > 1 ? B - 2 : 0;
+}
+
+// the schedule against the buffer's steps (checked dims)
+int check_schedule(const Phase &p)
+{
+    const int64_t L = p.d->num_steps;
+    if (p.shuffled) {
+        if (p.batch_size < 1 || L / p.batch_size < 1)
+            return failf(MARLNAV_EINVAL,
+                         "shuffle: batch_size=%lld gives no minibatch of %lld steps",
+                         (long long)p.batch_size, (long long)L);
+        return 0;
+    }
+    if (p.num_batches < 1)
+        return failf(MARLNAV_EINVAL, "train: num_batches=%lld < 1", (long long)p.num_batches);
+    if (!p.bounds) return marlnav_internal_fail(MARLNAV_EINVAL, "train: bounds is NULL");
+    for (int64_t j = 0; j < p.num_batches; ++j) {
+        const int64_t lo = p.bounds[2 * j], hi = p.bounds[2 * j + 1];
+        if (lo < 0 || hi <= lo || hi > L)
+            return failf(MARLNAV_EINVAL,
+                         "train: bounds[%lld]=(%lld, %lld) is not a non-empty range of the %lld "
+                         "steps", (long long)j, (long long)lo, (long long)hi, (long long)L);
+    }
+    return 0;
+}
+
+// the structs of minibatch j: dims of its steps, its loss cell; contiguous:
+// the data pointers at its first step; shuffled: at step 0 of the storage and
+// -> its entries of epoch e's permutation
+const int32_t *minibatch(const Phase &p, int64_t e, int64_t j, double *loss, MarlnavPpoDims *md,
+                         MarlnavPpoBuffers *mb)
+{
+    const MarlnavPpoDims *d = p.d;
+    const MarlnavPpoBuffers *b = p.b;
+    *md = *d;
+    md->num_steps = minibatch_steps(p, j);
+    *mb = *b;
+    mb->loss = loss;
+    if (p.shuffled) return p.table + e * d->num_steps + j * p.batch_size;
+    const int64_t rows = p.bounds[2 * j] * d->num_parallel, arows = rows * d->num_agents;
+    mb->obs = b->obs + arows * d->obs_dim;
+    if (b->actions) mb->actions = b->actions + arows * 2;
+    if (b->log_probs) mb->log_probs = b->log_probs + arows;
+    if (b->values) mb->values = b->values + rows;
+    mb->returns = b->returns + rows;
+    return nullptr;
+}
+
+// the workspace of the schedule's largest minibatch (monitored: of the
+// diagnostic variant), in doubles
+int64_t phase_work_size(const Phase &p)
+{
+    if (marlnav_ppo_work_size(p.d) < 0) return MARLNAV_EINVAL;
+    const int rc = check_schedule(p);
+    if (rc) return rc;
     int64_t need = 0;
-    const int64_t B = L / batch_size;
-    for (int64_t j = B > 1 ? B - 2 : 0; j < B; ++j) {  // the two sizes an epoch has
-        MarlnavPpoDims md = *d;
-        md.num_steps = shuffled_steps(L, batch_size, j);
-        const int64_t w = diag ? marlnav_ppo_diag_work_size(&md) : marlnav_ppo_work_size(&md);
+    MarlnavPpoDims md = *p.d;
+    for (int64_t j = first_size(p); j < num_minibatches(p); ++j) {
+        md.num_steps = minibatch_steps(p, j);
+        const int64_t w =
+            p.monitored ? marlnav_ppo_diag_work_size(&md) : marlnav_ppo_work_size(&md);
         if (w < 0) return w;
         if (w > need) need = w;
     }
     return need;
+}
+
+// every check of a phase call before its first launch
+int check_phase(const Phase &p)
+{
+    const int network = p.network;
+    if (p.monitored && network == MARLNAV_NETWORK_CRITIC)
+        return marlnav_internal_fail(
+            MARLNAV_EINVAL, p.shuffled ? "train: target_kl / diag_log / stop monitor the actor; "
+                                         "network is MARLNAV_NETWORK_CRITIC"
+                                       : "train: the monitored phase is the actor's; network is "
+                                         "MARLNAV_NETWORK_CRITIC");
+    if (!p.clipped && (p.clip.norm_work || p.clip.norm_out))
+        return marlnav_internal_fail(MARLNAV_EINVAL,
+                                     "clip: norm_work and norm_log must be NULL with "
+                                     "max_norm = MARLNAV_MAX_NORM_NONE");
+    int rc = 0;
+    if (p.shuffled) {
+        if (marlnav_ppo_work_size(p.d) < 0) return MARLNAV_EINVAL;
+        rc = check_schedule(p);
+        if (rc) return rc;
+        rc = check_permutations(p.d->num_steps, p.num_epochs, network, p.counter, p.table);
+        if (rc) return rc;
+    }
+    if (network != MARLNAV_NETWORK_ACTOR && network != MARLNAV_NETWORK_CRITIC)
+        return failf(MARLNAV_EINVAL, "train: network=%d must be MARLNAV_NETWORK_ACTOR or _CRITIC", network);
+    if (p.advantage_mode != MARLNAV_ADVANTAGE_REFERENCE && p.advantage_mode != MARLNAV_ADVANTAGE_ENV)
+        return failf(MARLNAV_EINVAL, "train: advantage_mode=%d must be MARLNAV_ADVANTAGE_REFERENCE or _ENV",
+                     p.advantage_mode);
+    // the own-env pairing is the actor's: it reads no values
+    const bool need_values =
+        network == MARLNAV_NETWORK_CRITIC || p.advantage_mode == MARLNAV_ADVANTAGE_REFERENCE;
+    if (marlnav_ppo_work_size(p.d) < 0) return MARLNAV_EINVAL;
+    const MarlnavPpoBuffers *b = p.b;
+    if (!b) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo buffers is NULL");
+    if (p.num_epochs < 1)
+        return failf(MARLNAV_EINVAL, "train: num_epochs=%lld < 1", (long long)p.num_epochs);
+    if (!p.shuffled) rc = check_schedule(p);
+    if (rc) return rc;
+    if (!p.loss_log) return marlnav_internal_fail(MARLNAV_EINVAL, "train: loss_log is NULL");
+    if (addr(p.loss_log) & 7u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "train: loss_log must be 8-byte aligned");
+    rc = check_adam(p.ad, p.ab);
+    if (rc) return rc;
+    rc = check_table(network, p.d, b, p.ad, p.ab);
+    if (rc) return rc;
+    if (p.clipped) rc = check_clip(p.clip.max_norm, p.clip.norm_work, p.clip.norm_out, "norm_log");
+    if (rc) return rc;
+    if (!b->obs) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer obs is NULL");
+    if (need_values && !b->values)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer values is NULL");
+    if (!b->returns) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: buffer returns is NULL");
+    MarlnavPpoDims md;
+    MarlnavPpoBuffers mb;
+    for (int64_t j = first_size(p); j < num_minibatches(p); ++j) {  // dims and buffers
+        minibatch(p, 0, j, p.loss_log, &md, &mb);
+        rc = marlnav_internal_ppo_validate(network, p.advantage_mode, &md, &mb);
+        if (rc) return rc;
+    }
+    if (!p.monitored) return 0;
+    if (!(p.target_kl > 0.0))  // a NaN is not greater
+        return failf(MARLNAV_EINVAL, "train: target_kl=%g must be > 0 (+inf: monitor only)",
+                     p.target_kl);
+    if (!p.diag_log) return marlnav_internal_fail(MARLNAV_EINVAL, "train: diag_log is NULL");
+    if (addr(p.diag_log) & 7u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "train: diag_log must be 8-byte aligned");
+    if (!p.stop) return marlnav_internal_fail(MARLNAV_EINVAL, "train: stop is NULL");
+    if (addr(p.stop) & 7u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "train: stop must be 8-byte aligned");
+    return 0;
+}
+
+// the phase: its checks, the permutations of a shuffled schedule, then
+// num_epochs x num_minibatches updates, epoch-major. Which launches an update
+// is, marlnav_ppo.hip decides ("The launch paths").
+int run_phase(const Phase &p, void *stream)
+{
+    int rc = check_phase(p);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (p.shuffled) {
+        enqueue_permutations(p.d->num_steps, p.num_epochs, p.seed, p.network, p.counter, p.table,
+                             s);
+        rc = launch_status();
+        if (rc) return rc;
+    }
+    PpoUpdate u = {};
+    u.network = p.network;
+    u.epsilon = p.epsilon;
+    u.ent_const = p.ent_const;
+    u.advantage_mode = p.advantage_mode;
+    u.stop = p.stop;
+    u.target_kl = p.target_kl;
+    u.ad = p.ad;
+    u.ab = p.ab;
+    u.may_fold = true;
+    ClipArgs clip = p.clip;
+    if (p.clipped) u.clip = &clip;
+    MarlnavPpoDims md;
+    MarlnavPpoBuffers mb;
+    const int64_t B = num_minibatches(p);
+    for (int64_t e = 0, k = 0; e < p.num_epochs; ++e)
+        for (int64_t j = 0; j < B; ++j, ++k) {
+            u.steps = minibatch(p, e, j, p.loss_log + k, &md, &mb);
+            u.k = k;
+            if (p.monitored) u.diag_row = p.diag_log + MARLNAV_DIAG_ROW * k;
+            if (p.clip.norm_out) clip.norm_out = p.clip.norm_out + k;
+            rc = enqueue_update(u, &md, &mb, s);
+            if (rc) return rc;
+        }
+    return 0;
+}
+
+Phase make_phase(int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                       const int64_t *bounds, int64_t num_batches, int64_t num_epochs,
+                       double epsilon, double ent_const, const MarlnavAdamDims *ad,
+                       const MarlnavAdamBuffers *ab, double *loss_log, int advantage_mode)
+{
+    Phase p = {};
+    p.network = network;
+    p.d = d;
+    p.b = b;
+    p.bounds = bounds;
+    p.num_batches = num_batches;
+    p.num_epochs = num_epochs;
+    p.epsilon = epsilon;
+    p.ent_const = ent_const;
+    p.ad = ad;
+    p.ab = ab;
+    p.loss_log = loss_log;
+    p.advantage_mode = advantage_mode;
+    return p;
+}
+
+}  // namespace
+
+extern "C" int64_t marlnav_ppo_train_work_size(const MarlnavPpoDims *d, const int64_t *bounds,
+                                               int64_t num_batches)
+{
+    Phase p = {};
+    p.d = d;
+    p.bounds = bounds;
+    p.num_batches = num_batches;
+    return phase_work_size(p);
+}
+
+extern "C" int64_t marlnav_ppo_train_diag_work_size(const MarlnavPpoDims *d,
+                                                    const int64_t *bounds, int64_t num_batches)
+{
+    Phase p = {};
+    p.d = d;
+    p.bounds = bounds;
+    p.num_batches = num_batches;
+    p.monitored = true;
+    return phase_work_size(p);
+}
+
+extern "C" int64_t marlnav_ppo_train_shuffled_work_size(const MarlnavPpoDims *d,
+                                                        int64_t batch_size, int diag)
+{
+    Phase p = {};
+    p.d = d;
+    p.shuffled = true;
+    p.batch_size = batch_size;
+    p.monitored = diag != 0;
+    return phase_work_size(p);
+}
+
+extern "C" int marlnav_ppo_train_phase_mode(int network, const MarlnavPpoDims *d,
+                                            const MarlnavPpoBuffers *b, const int64_t *bounds,
+                                            int64_t num_batches, int64_t num_epochs,
+                                            double epsilon, double ent_const,
+                                            const MarlnavAdamDims *ad,
+                                            const MarlnavAdamBuffers *ab, double *loss_log,
+                                            int advantage_mode, void *stream)
+{
+    return run_phase(make_phase(network, d, b, bounds, num_batches, num_epochs, epsilon,
+                                      ent_const, ad, ab, loss_log, advantage_mode), stream);
+}
+
+extern "C" int marlnav_ppo_train_phase_clipped(int network, const MarlnavPpoDims *d,
+                                               const MarlnavPpoBuffers *b, const int64_t *bounds,
+                                               int64_t num_batches, int64_t num_epochs,
+                                               double epsilon, double ent_const,
+                                               const MarlnavAdamDims *ad,
+                                               const MarlnavAdamBuffers *ab, double *loss_log,
+                                               int advantage_mode, double max_norm,
+                                               double *norm_work, double *norm_log, void *stream)
+{
+    Phase p = make_phase(network, d, b, bounds, num_batches, num_epochs, epsilon, ent_const,
+                               ad, ab, loss_log, advantage_mode);
+    p.clipped = true;
+    p.clip = {max_norm, norm_work, norm_log};
+    return run_phase(p, stream);
+}
+
+extern "C" int marlnav_ppo_train_phase(int network, const MarlnavPpoDims *d,
+                                       const MarlnavPpoBuffers *b, const int64_t *bounds,
+                                       int64_t num_batches, int64_t num_epochs, double epsilon,
+                                       double ent_const, const MarlnavAdamDims *ad,
+                                       const MarlnavAdamBuffers *ab, double *loss_log,
+                                       void *stream)
+{
+    return marlnav_ppo_train_phase_mode(network, d, b, bounds, num_batches, num_epochs, epsilon,
+                                        ent_const, ad, ab, loss_log, MARLNAV_ADVANTAGE_REFERENCE,
+                                        stream);
+}
+
+extern "C" int marlnav_ppo_train_phase_monitored(
+    int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, const int64_t *bounds,
+    int64_t num_batches, int64_t num_epochs, double epsilon, double ent_const,
+    const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, double *loss_log, int advantage_mode,
+    double max_norm, double *norm_work, double *norm_log, double target_kl, double *diag_log,
+    int64_t *stop, void *stream)
+{
+    Phase p = make_phase(network, d, b, bounds, num_batches, num_epochs, epsilon, ent_const,
+                               ad, ab, loss_log, advantage_mode);
+    p.clipped = max_norm != MARLNAV_MAX_NORM_NONE;  // a NaN is refused by check_clip
+    p.clip = {max_norm, norm_work, norm_log};
+    p.monitored = true;
+    p.target_kl = target_kl;
+    p.diag_log = diag_log;
+    p.stop = stop;
+    return run_phase(p, stream);
 }
 
 extern "C" int marlnav_ppo_train_phase_shuffled(
@@ -986,79 +1011,20 @@ extern "C" int marlnav_ppo_train_phase_shuffled(
     double *norm_work, double *norm_log, double target_kl, double *diag_log, int64_t *stop,
     uint64_t seed, uint64_t *counter, int32_t *table, void *stream)
 {
-    // ---- every check before the first launch
-    const bool monitored = target_kl != 0.0 || diag_log || stop;
-    if (monitored && network == MARLNAV_NETWORK_CRITIC)
-        return marlnav_internal_fail(MARLNAV_EINVAL,
-                                     "train: target_kl / diag_log / stop monitor the actor; "
-                                     "network is MARLNAV_NETWORK_CRITIC");
-    const bool clipped = max_norm != MARLNAV_MAX_NORM_NONE;  // a NaN is refused by check_clip
-    if (!clipped && (norm_work || norm_log))
-        return marlnav_internal_fail(MARLNAV_EINVAL,
-                                     "clip: norm_work and norm_log must be NULL with "
-                                     "max_norm = MARLNAV_MAX_NORM_NONE");
-    if (marlnav_ppo_work_size(d) < 0) return MARLNAV_EINVAL;
-    const int64_t L = d->num_steps;
-    if (batch_size < 1 || L / batch_size < 1)
-        return failf(MARLNAV_EINVAL, "shuffle: batch_size=%lld gives no minibatch of %lld steps",
-                     (long long)batch_size, (long long)L);
-    int rc = check_permutations(L, num_epochs, network, counter, table);
-    if (rc) return rc;
-    const int64_t B = L / batch_size;
-    // the contiguous phase's checks, over the whole buffer as one range
-    const int64_t whole[2] = {0, L};
-    const ClipArgs clip = {max_norm, norm_work, norm_log};
-    rc = check_train_phase(network, d, b, whole, 1, num_epochs, epsilon, ent_const, ad, ab,
-                           loss_log, advantage_mode, clipped ? &clip : nullptr, stream);
-    if (rc) return rc;
-    if (monitored) {
-        if (!(target_kl > 0.0))  // a NaN is not greater
-            return failf(MARLNAV_EINVAL, "train: target_kl=%g must be > 0 (+inf: monitor only)",
-                         target_kl);
-        if (!diag_log) return marlnav_internal_fail(MARLNAV_EINVAL, "train: diag_log is NULL");
-        if (addr(diag_log) & 7u)
-            return marlnav_internal_fail(MARLNAV_EINVAL, "train: diag_log must be 8-byte aligned");
-        if (!stop) return marlnav_internal_fail(MARLNAV_EINVAL, "train: stop is NULL");
-        if (addr(stop) & 7u)
-            return marlnav_internal_fail(MARLNAV_EINVAL, "train: stop must be 8-byte aligned");
-    }
-    MarlnavPpoDims md = *d;
-    MarlnavPpoBuffers mb = *b;
-    for (int64_t j = B > 1 ? B - 2 : 0; j < B; ++j) {  // dims of the two minibatch sizes
-        md.num_steps = shuffled_steps(L, batch_size, j);
-        rc = marlnav_internal_ppo_grad_steps(network, &md, &mb, table, epsilon, ent_const,
-                                             advantage_mode, nullptr, nullptr, 0.0, 0, stream, 1);
-        if (rc) return rc;
-    }
-    // ---- the permutations, then num_epochs x B updates, epoch-major: the gather
-    // gradient launches and the Adam launches (clipped and gated where asked).
-    // Nothing is folded: the finish kernels' folds have no gather variants.
-    enqueue_permutations(L, num_epochs, seed, network, counter, table, (hipStream_t)stream);
-    rc = launch_status();
-    if (rc) return rc;
-    int64_t k = 0;
-    for (int64_t e = 0; e < num_epochs; ++e)
-        for (int64_t j = 0; j < B; ++j, ++k) {
-            md.num_steps = shuffled_steps(L, batch_size, j);
-            mb.loss = loss_log + k;
-            rc = marlnav_internal_ppo_grad_steps(
-                network, &md, &mb, table + e * L + j * batch_size, epsilon, ent_const,
-                advantage_mode, monitored ? diag_log + MARLNAV_DIAG_ROW * k : nullptr, stop,
-                target_kl, k, stream, 0);
-            if (rc) return rc;
-            const ClipArgs ck = {max_norm, norm_work, norm_log ? norm_log + k : nullptr};
-            rc = enqueue_adam(ad, ab, (hipStream_t)stream, clipped ? &ck : nullptr,
-                              monitored ? stop : nullptr);
-            if (rc) return rc;
-        }
-    return 0;
-}
-
-extern "C" int marlnav_debug_clip_fold(int on)
-{
-    const int before = g_clip_fold;
-    if (on == 0 || on == 1) g_clip_fold = on;
-    return before;
+    Phase p = make_phase(network, d, b, nullptr, 0, num_epochs, epsilon, ent_const, ad, ab,
+                               loss_log, advantage_mode);
+    p.shuffled = true;
+    p.batch_size = batch_size;
+    p.seed = seed;
+    p.counter = counter;
+    p.table = table;
+    p.clipped = max_norm != MARLNAV_MAX_NORM_NONE;  // a NaN is refused by check_clip
+    p.clip = {max_norm, norm_work, norm_log};
+    p.monitored = target_kl != 0.0 || diag_log || stop;
+    p.target_kl = target_kl;
+    p.diag_log = diag_log;
+    p.stop = stop;
+    return run_phase(p, stream);
 }
 
 // =========================================================================

@@ -37,12 +37,11 @@
 
 #include "../../include/marlnav.h"
 
-__attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const char *msg);
+#include "host_util.h"
 
 namespace {
 
 #include "policy_forward.h"
-#include "host_util.h"
 
 constexpr int kRowsPerBlock = kThreads;  // agent rows of a block: one per thread (measured
                                          // against 64, 128, 512, 1024: DESIGN.md §13)

@@ -60,12 +60,11 @@
 
 #include "../../include/marlnav.h"
 
-__attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const char *msg);
+#include "host_util.h"
 
 namespace {
 
 #include "policy_forward.h"
-#include "host_util.h"
 
 constexpr int kEnvsPerBlock = 64;
 // dynamic LDS floats of a block: the collapse, then the critic partials

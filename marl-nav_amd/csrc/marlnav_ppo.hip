@@ -55,16 +55,14 @@
 
 #include "../../include/marlnav.h"
 #include "adam_element.h"
-
-__attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const char *msg);
+#include "host_util.h"
+#include "ppo_update.h"
 
 namespace {
 
-// the block shape, the policy's limits, kLog2Pi and relu_t; block_sum; failf,
-// launch_status and the shape check
+// the block shape, the policy's limits, kLog2Pi and relu_t; block_sum
 #include "policy_forward.h"
 #include "block_sum.h"
-#include "host_util.h"
 
 // ---- actor tiling
 constexpr int kActorTile = kThreads;       // rows per tile
@@ -1339,26 +1337,92 @@ int check_critic_bufs(const MarlnavPpoBuffers *b)
     return 0;
 }
 
-// checked arguments only. adv / fold NULL: the two launches of
-// marlnav_ppo_actor_grad; given: the same two with the Adam step folded in.
-int enqueue_actor(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
-                  double ent_const, int advantage_mode, const AdvArgs *adv, const FoldArgs *fold,
-                  hipStream_t s, const ClipFoldArgs *clip = nullptr, const DiagArgs *dg = nullptr,
-                  const int32_t *steps = nullptr)
+int check_steps(const int32_t *steps)
+{
+    if (!steps) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: steps is NULL");
+    if (reinterpret_cast<uintptr_t>(steps) & 3u)
+        return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: steps must be 4-byte aligned");
+    return 0;
+}
+
+// ---- which launches an update is ("The launch paths")
+// whether the clipped phase folds the actor's clip and Adam step into
+// actor_finish (marlnav_debug_clip_fold; the default is the measured decision
+// of DESIGN.md §16)
+int g_clip_fold = MARLNAV_CLIP_FOLD_DEFAULT;
+
+// actor_finish is one block: its folded update walks the actor's elements
+// 256 at a time, about 4 us per 1000 elements, against the 5 us the two
+// launches of marlnav_adam_step cost. Measured (DESIGN.md §14): a gain of
+// 1.3-2 us per update at 854 elements (3 x 3, H = 50), 0.5 us at 1354 (3 x 8),
+// a loss of 14 us at 5054 (16 x 32). So the actor folds up to 1024 elements
+// and keeps the separate Adam launches beyond. critic_finish is thread =
+// element over many blocks; its fold gains 4-6 us per update up to 131 072
+// env rows and loses 2-3 us at 524 288 (65536 x 3 x 3 of 8 steps), where the
+// pass runs for 270 us and the separate Adam launches' dispatch hides behind
+// it: the critic folds up to 2^17 env rows.
+constexpr int64_t kActorFoldMaxElements = 1024;
+constexpr int64_t kCriticFoldMaxRows = (int64_t)1 << 17;
+
+// where the update's Adam step runs: in launches of its own (the caller's), in
+// the finish launch, or, clipped, in actor_finish with the norm formed in-block
+enum Fold { kNoFold, kFold, kClipFold };
+
+Fold fold_of(const PpoUpdate &u, const MarlnavPpoDims *d)
+{
+    // the folds have no gather variants, and a monitored update that stops must
+    // not step
+    if (!u.ad || !u.may_fold || u.steps || u.diag_row) return kNoFold;
+    if (u.network == MARLNAV_NETWORK_ACTOR) {
+        const int64_t H = d->hidden_size, D = d->obs_dim;
+        if (H * (D + 1) + 4 * H + 4 > kActorFoldMaxElements) return kNoFold;
+        if (u.clip) return g_clip_fold ? kClipFold : kNoFold;
+        return kFold;
+    }
+    // critic_finish updates elements before the norm exists
+    if (u.clip || d->num_steps * d->num_parallel > kCriticFoldMaxRows) return kNoFold;
+    return kFold;
+}
+
+void fold_args(const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, AdvArgs *adv, FoldArgs *f)
+{
+    adv->state = static_cast<AdamState *>(ab->state);
+    adv->lr = ad->lr;
+    adv->beta1 = ad->beta1;
+    adv->beta2 = ad->beta2;
+    for (int i = 0; i < 6; ++i) {
+        const bool used = i < ad->num_tensors;
+        f->param[i] = used ? ab->param[i] : nullptr;
+        f->exp_avg[i] = used ? ab->exp_avg[i] : nullptr;
+        f->exp_avg_sq[i] = used ? ab->exp_avg_sq[i] : nullptr;
+    }
+    f->state = adv->state;
+    f->beta1 = ad->beta1;
+    f->beta2 = ad->beta2;
+    f->omb1 = 1.0 - ad->beta1;
+    f->omb2 = 1.0 - ad->beta2;
+    f->eps = ad->eps;
+    f->maximize = ad->maximize;
+}
+
+// checked arguments only: the two launches of the actor's update, the
+// template packs chosen from the update and its fold
+int enqueue_actor(const PpoUpdate &u, Fold fold, const MarlnavPpoDims *d,
+                  const MarlnavPpoBuffers *b, hipStream_t s)
 {
     PpoArgs a = make_args(d, b);
     actor_grid(a.M, a.rows_per_block, a.nblocks);
     // the reference's Python scalars 1 - margin, 1 + margin and ent_const meet
     // fp32 tensors: rounded to fp32 once
-    a.clip_lo = (float)(1.0 - epsilon);
-    a.clip_hi = (float)(1.0 + epsilon);
-    a.ent_f = (float)ent_const;
+    a.clip_lo = (float)(1.0 - u.epsilon);
+    a.clip_hi = (float)(1.0 + u.epsilon);
+    a.ent_f = (float)u.ent_const;
     const int nS = 4 * (a.D + 1) + 2;
     const int groups = nS >= kThreads ? 1 : kThreads / nS;
     const size_t fin_lds = sizeof(double) * (size_t)nS * (1 + (groups > 1 ? groups : 0));
     const dim3 grid((unsigned)a.nblocks), blk(kThreads);
     const size_t lds = actor_lds_bytes(a.D);
-    const bool env = advantage_mode == MARLNAV_ADVANTAGE_ENV;
+    const bool env = u.advantage_mode == MARLNAV_ADVANTAGE_ENV;
     // the pass launch over `g` (PpoArgs, or GatherArgs: the gather variant) with
     // the trailing pack x
     auto pass = [&](const auto &g, auto... x) {
@@ -1372,26 +1436,32 @@ int enqueue_actor(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double ep
         hipLaunchKernelGGL(actor_finish, dim3(1), dim3(kThreads), bytes, s, a, x...);
     };
     const size_t dg_lds = fin_lds + sizeof(double) * kWaves;
-    if (steps) {  // the gather variants (adv, fold, clip are NULL): nothing is folded
+    const DiagArgs dg = {u.diag_row, u.stop, u.target_kl, u.k, u.k == 0 ? 1 : 0};
+    AdvArgs adv;
+    ClipFoldArgs c;
+    if (fold != kNoFold) fold_args(u.ad, u.ab, &adv, &c.f);
+    if (u.steps) {  // the gather variants
         GatherArgs ga;
         static_cast<PpoArgs &>(ga) = a;
-        ga.steps = steps;
-        if (dg) {
-            pass(ga, *dg);
-            finish(dg_lds, *dg);
+        ga.steps = u.steps;
+        if (u.diag_row) {
+            pass(ga, dg);
+            finish(dg_lds, dg);
         } else {
             pass(ga);
             finish(fin_lds);
         }
-    } else if (dg) {  // the diagnostic variant (adv, fold, clip are NULL)
-        pass(a, *dg);
-        finish(dg_lds, *dg);
-    } else if (clip) {  // the clipped update folded in (fold is NULL)
-        pass(a, *adv);
-        finish(fin_lds, *clip);
-    } else if (fold) {
-        pass(a, *adv);
-        finish(fin_lds, *fold);
+    } else if (u.diag_row) {  // the diagnostic variant
+        pass(a, dg);
+        finish(dg_lds, dg);
+    } else if (fold == kClipFold) {  // norm, clip and update inside actor_finish
+        c.max_norm = u.clip->max_norm;
+        c.norm_out = u.clip->norm_out;
+        pass(a, adv);
+        finish(fin_lds, c);
+    } else if (fold == kFold) {
+        pass(a, adv);
+        finish(fin_lds, c.f);
     } else {
         pass(a);
         finish(fin_lds);
@@ -1399,15 +1469,14 @@ int enqueue_actor(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double ep
     return launch_status();
 }
 
-int enqueue_critic(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
-                   const AdvArgs *adv, const FoldArgs *fold, hipStream_t s,
-                   const int32_t *steps = nullptr)
+int enqueue_critic(const PpoUpdate &u, Fold fold, const MarlnavPpoDims *d,
+                   const MarlnavPpoBuffers *b, hipStream_t s)
 {
     PpoArgs a = make_args(d, b);
     const int AD = a.A * a.D;
     const CriticTiling ct = critic_tiling(AD, a.H);
     critic_grid(a.N, AD, a.H, ct, a.rows_per_block, a.nblocks);
-    a.eps_f = (float)epsilon;  // values - epsilon: a Python scalar against an fp32 tensor
+    a.eps_f = (float)u.epsilon;  // values - epsilon: a Python scalar against an fp32 tensor
     const dim3 grid((unsigned)a.nblocks, (unsigned)(ct.ncoltile * ct.nugroup));
     // (with a gather too: every step starts a multiple of P A D floats after step 0)
     const int vec4 = AD % 4 == 0 && (reinterpret_cast<uintptr_t>(b->obs) & 15u) == 0;
@@ -1451,23 +1520,80 @@ int enqueue_critic(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double e
                                (float *)nullptr, 0, vec4, x...);
         }
     };
-    if (steps) {  // adv, fold are NULL: nothing is folded
+    AdvArgs adv;
+    FoldArgs f;
+    if (fold == kFold) fold_args(u.ad, u.ab, &adv, &f);
+    if (u.steps) {  // the gather variants
         GatherArgs ga;
         static_cast<PpoArgs &>(ga) = a;
-        ga.steps = steps;
+        ga.steps = u.steps;
         pass(ga);
-    } else if (fold) {
-        pass(a, *adv);
+    } else if (fold == kFold) {
+        pass(a, adv);
     } else {
         pass(a);
     }
     const int64_t nout = critic_stride(AD, a.H);
     const dim3 ogrid((unsigned)((nout + kThreads - 1) / kThreads));
-    if (fold)
-        hipLaunchKernelGGL(critic_finish, ogrid, dim3(kThreads), 0, s, a, *fold);
+    if (fold == kFold)
+        hipLaunchKernelGGL(critic_finish, ogrid, dim3(kThreads), 0, s, a, f);
     else
         hipLaunchKernelGGL(critic_finish, ogrid, dim3(kThreads), 0, s, a);
     return launch_status();
+}
+
+// a gradient-only update: no optimiser, so nothing is folded and no step owed
+PpoUpdate grad_only(int network, double epsilon, double ent_const, int advantage_mode,
+                    const int32_t *steps, double *diag)
+{
+    PpoUpdate u = {};
+    u.network = network;
+    u.epsilon = epsilon;
+    u.ent_const = ent_const;
+    u.advantage_mode = advantage_mode;
+    u.steps = steps;
+    u.diag_row = diag;  // no stop: status 0
+    u.target_kl = __builtin_inf();
+    return u;
+}
+
+}  // namespace
+
+int marlnav_internal_ppo_validate(int network, int advantage_mode, const MarlnavPpoDims *d,
+                                  const MarlnavPpoBuffers *b)
+{
+    int rc = check_dims(d);
+    if (rc) return rc;
+    if (network != MARLNAV_NETWORK_ACTOR) return check_critic_bufs(b);
+    rc = check_mode(advantage_mode);
+    return rc ? rc : check_actor_bufs(b, advantage_mode);
+}
+
+int marlnav_internal_ppo_enqueue(const PpoUpdate *u, const MarlnavPpoDims *d,
+                                 const MarlnavPpoBuffers *b, void *stream, bool *adam_owed)
+{
+    const Fold fold = fold_of(*u, d);
+    *adam_owed = u->ad && fold == kNoFold;
+    return u->network == MARLNAV_NETWORK_ACTOR
+               ? enqueue_actor(*u, fold, d, b, (hipStream_t)stream)
+               : enqueue_critic(*u, fold, d, b, (hipStream_t)stream);
+}
+
+extern "C" int marlnav_debug_clip_fold(int on)
+{
+    const int before = g_clip_fold;
+    if (on == 0 || on == 1) g_clip_fold = on;
+    return before;
+}
+
+namespace {
+
+// a gradient-only entry behind its own checks
+int enqueue_grad(const PpoUpdate &u, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
+                 void *stream)
+{
+    bool owed;
+    return marlnav_internal_ppo_enqueue(&u, d, b, stream, &owed);
 }
 
 }  // namespace
@@ -1476,57 +1602,24 @@ extern "C" int marlnav_ppo_actor_grad_mode(const MarlnavPpoDims *d, const Marlna
                                            double epsilon, double ent_const, int advantage_mode,
                                            void *stream)
 {
-    int rc = check_dims(d);
+    const int rc = marlnav_internal_ppo_validate(MARLNAV_NETWORK_ACTOR, advantage_mode, d, b);
     if (rc) return rc;
-    rc = check_mode(advantage_mode);
-    if (rc) return rc;
-    rc = check_actor_bufs(b, advantage_mode);
-    if (rc) return rc;
-    return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
-                         (hipStream_t)stream);
+    return enqueue_grad(grad_only(MARLNAV_NETWORK_ACTOR, epsilon, ent_const, advantage_mode,
+                                  nullptr, nullptr), d, b, stream);
 }
 
 extern "C" int marlnav_ppo_actor_grad_diag(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
                                            double epsilon, double ent_const, int advantage_mode,
                                            double *diag, void *stream)
 {
-    int rc = check_dims(d);
-    if (rc) return rc;
-    rc = check_mode(advantage_mode);
-    if (rc) return rc;
-    rc = check_actor_bufs(b, advantage_mode);
+    const int rc = marlnav_internal_ppo_validate(MARLNAV_NETWORK_ACTOR, advantage_mode, d, b);
     if (rc) return rc;
     if (!diag) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: diag is NULL");
     if (reinterpret_cast<uintptr_t>(diag) & 7u)
         return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: diag must be 8-byte aligned");
-    const DiagArgs dg = {diag, nullptr, __builtin_inf(), 0, 1};
-    return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
-                         (hipStream_t)stream, nullptr, &dg);
+    return enqueue_grad(grad_only(MARLNAV_NETWORK_ACTOR, epsilon, ent_const, advantage_mode,
+                                  nullptr, diag), d, b, stream);
 }
-
-// Update k of marlnav_ppo_train_phase_monitored (marlnav_adam.hip, which has
-// checked every argument): the diagnostic gradient launches, which write
-// diag_row and loss, decide the stop and, behind it, do nothing.
-__attribute__((visibility("hidden"))) int marlnav_internal_ppo_actor_diag(
-    const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon, double ent_const,
-    int advantage_mode, double *diag_row, int64_t *stop, double target_kl, int64_t k, void *stream)
-{
-    const DiagArgs dg = {diag_row, stop, target_kl, k, k == 0 ? 1 : 0};
-    return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
-                         (hipStream_t)stream, nullptr, &dg);
-}
-
-namespace {
-
-int check_steps(const int32_t *steps)
-{
-    if (!steps) return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: steps is NULL");
-    if (reinterpret_cast<uintptr_t>(steps) & 3u)
-        return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: steps must be 4-byte aligned");
-    return 0;
-}
-
-}  // namespace
 
 // The gather forms: logical step slot s of the minibatch is
 // step steps[s] of the storage whose step 0 the data pointers address.
@@ -1535,51 +1628,25 @@ extern "C" int marlnav_ppo_actor_grad_steps(const MarlnavPpoDims *d, const Marln
                                             double ent_const, int advantage_mode, double *diag,
                                             void *stream)
 {
-    int rc = check_dims(d);
-    if (rc) return rc;
-    rc = check_mode(advantage_mode);
-    if (rc) return rc;
-    rc = check_actor_bufs(b, advantage_mode);
+    int rc = marlnav_internal_ppo_validate(MARLNAV_NETWORK_ACTOR, advantage_mode, d, b);
     if (rc) return rc;
     rc = check_steps(steps);
     if (rc) return rc;
     if (reinterpret_cast<uintptr_t>(diag) & 7u)
         return marlnav_internal_fail(MARLNAV_EINVAL, "ppo: diag must be 8-byte aligned");
-    const DiagArgs dg = {diag, nullptr, __builtin_inf(), 0, 1};
-    return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
-                         (hipStream_t)stream, nullptr, diag ? &dg : nullptr, steps);
+    return enqueue_grad(grad_only(MARLNAV_NETWORK_ACTOR, epsilon, ent_const, advantage_mode,
+                                  steps, diag), d, b, stream);
 }
 
 extern "C" int marlnav_ppo_critic_grad_steps(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
                                              const int32_t *steps, double epsilon, void *stream)
 {
-    int rc = check_dims(d);
-    if (rc) return rc;
-    rc = check_critic_bufs(b);
+    int rc = marlnav_internal_ppo_validate(MARLNAV_NETWORK_CRITIC, 0, d, b);
     if (rc) return rc;
     rc = check_steps(steps);
     if (rc) return rc;
-    return enqueue_critic(d, b, epsilon, nullptr, nullptr, (hipStream_t)stream, steps);
-}
-
-// Update k of marlnav_ppo_train_phase_shuffled (marlnav_adam.hip, which has
-// checked every argument): the gather gradient launches of one minibatch; with
-// diag_row the diagnostic variant and the stop, as marlnav_internal_ppo_actor_diag.
-// check_only: the dims and buffer checks and nothing launched.
-__attribute__((visibility("hidden"))) int marlnav_internal_ppo_grad_steps(
-    int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, const int32_t *steps,
-    double epsilon, double ent_const, int advantage_mode, double *diag_row, int64_t *stop,
-    double target_kl, int64_t k, void *stream, int check_only)
-{
-    int rc = check_dims(d);
-    if (rc) return rc;
-    rc = network == 0 ? check_actor_bufs(b, advantage_mode) : check_critic_bufs(b);
-    if (rc || check_only) return rc;
-    if (network != 0)
-        return enqueue_critic(d, b, epsilon, nullptr, nullptr, (hipStream_t)stream, steps);
-    const DiagArgs dg = {diag_row, stop, target_kl, k, k == 0 ? 1 : 0};
-    return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
-                         (hipStream_t)stream, nullptr, diag_row ? &dg : nullptr, steps);
+    return enqueue_grad(grad_only(MARLNAV_NETWORK_CRITIC, epsilon, 0.0, 0, steps, nullptr), d, b,
+                        stream);
 }
 
 extern "C" int marlnav_ppo_actor_grad(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
@@ -1592,104 +1659,8 @@ extern "C" int marlnav_ppo_actor_grad(const MarlnavPpoDims *d, const MarlnavPpoB
 extern "C" int marlnav_ppo_critic_grad(const MarlnavPpoDims *d, const MarlnavPpoBuffers *b,
                                        double epsilon, void *stream)
 {
-    int rc = check_dims(d);
+    const int rc = marlnav_internal_ppo_validate(MARLNAV_NETWORK_CRITIC, 0, d, b);
     if (rc) return rc;
-    rc = check_critic_bufs(b);
-    if (rc) return rc;
-    return enqueue_critic(d, b, epsilon, nullptr, nullptr, (hipStream_t)stream);
-}
-
-// actor_finish is one block: its folded update walks the actor's elements
-// 256 at a time, about 4 us per 1000 elements, against the 5 us the two
-// launches of marlnav_adam_step cost. Measured (DESIGN.md §14): a gain of
-// 1.3-2 us per update at 854 elements (3 x 3, H = 50), 0.5 us at 1354 (3 x 8),
-// a loss of 14 us at 5054 (16 x 32). So the actor folds up to 1024 elements
-// and keeps the separate Adam launches beyond. critic_finish is thread =
-// element over many blocks; its fold gains 4-6 us per update up to 131 072
-// env rows and loses 2-3 us at 524 288 (65536 x 3 x 3 of 8 steps), where the
-// pass runs for 270 us and the separate Adam launches' dispatch hides behind
-// it: the critic folds up to 2^17 env rows.
-constexpr int64_t kActorFoldMaxElements = 1024;
-constexpr int64_t kCriticFoldMaxRows = (int64_t)1 << 17;
-
-namespace {
-
-void fold_args(const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, AdvArgs *adv, FoldArgs *f)
-{
-    adv->state = static_cast<AdamState *>(ab->state);
-    adv->lr = ad->lr;
-    adv->beta1 = ad->beta1;
-    adv->beta2 = ad->beta2;
-    for (int i = 0; i < 6; ++i) {
-        const bool used = i < ad->num_tensors;
-        f->param[i] = used ? ab->param[i] : nullptr;
-        f->exp_avg[i] = used ? ab->exp_avg[i] : nullptr;
-        f->exp_avg_sq[i] = used ? ab->exp_avg_sq[i] : nullptr;
-    }
-    f->state = adv->state;
-    f->beta1 = ad->beta1;
-    f->beta2 = ad->beta2;
-    f->omb1 = 1.0 - ad->beta1;
-    f->omb2 = 1.0 - ad->beta2;
-    f->eps = ad->eps;
-    f->maximize = ad->maximize;
-}
-
-}  // namespace
-
-// One clipped actor update for marlnav_ppo_train_phase_clipped with the clip
-// and the Adam step inside actor_finish (two launches), where the actor is
-// within the fold limit: returns 0 with both launches enqueued, 1 with nothing
-// enqueued (a larger actor: the caller enqueues the unfolded update), negative
-// on an error. Checked arguments only, as marlnav_internal_ppo_fold.
-__attribute__((visibility("hidden"))) int marlnav_internal_ppo_actor_clip_fold(
-    const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon, double ent_const,
-    int advantage_mode, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab, double max_norm,
-    double *norm_out, void *stream)
-{
-    const int64_t H = d->hidden_size, D = d->obs_dim;
-    if (H * (D + 1) + 4 * H + 4 > kActorFoldMaxElements) return 1;
-    AdvArgs adv;
-    ClipFoldArgs c;
-    fold_args(ad, ab, &adv, &c.f);
-    c.max_norm = max_norm;
-    c.norm_out = norm_out;
-    return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, &adv, nullptr,
-                         (hipStream_t)stream, &c);
-}
-
-// One minibatch update for marlnav_ppo_train_phase (marlnav_adam.hip), which
-// has checked the Adam arguments and that the table is this network's own.
-// network 0: the actor, 1: the critic (advantage_mode, checked by the caller,
-// is the actor's). check_only: the dims and buffer checks of this update and
-// nothing launched. Returns 0 with the Adam step folded
-// into the finish launch, 1 with the gradient launches alone enqueued (the
-// caller then enqueues the Adam step), negative on an error.
-__attribute__((visibility("hidden"))) int marlnav_internal_ppo_fold(
-    int network, const MarlnavPpoDims *d, const MarlnavPpoBuffers *b, double epsilon,
-    double ent_const, int advantage_mode, const MarlnavAdamDims *ad, const MarlnavAdamBuffers *ab,
-    void *stream, int check_only)
-{
-    int rc = check_dims(d);
-    if (rc) return rc;
-    rc = network == 0 ? check_actor_bufs(b, advantage_mode) : check_critic_bufs(b);
-    if (rc || check_only) return rc;
-    if (network == 0) {
-        const int64_t H = d->hidden_size, D = d->obs_dim;
-        if (H * (D + 1) + 4 * H + 4 > kActorFoldMaxElements) {
-            rc = enqueue_actor(d, b, epsilon, ent_const, advantage_mode, nullptr, nullptr,
-                               (hipStream_t)stream);
-            return rc ? rc : 1;
-        }
-    } else if (d->num_steps * d->num_parallel > kCriticFoldMaxRows) {
-        rc = enqueue_critic(d, b, epsilon, nullptr, nullptr, (hipStream_t)stream);
-        return rc ? rc : 1;
-    }
-    AdvArgs adv;
-    FoldArgs f;
-    fold_args(ad, ab, &adv, &f);
-    if (network == 0)
-        return enqueue_actor(d, b, epsilon, ent_const, advantage_mode, &adv, &f,
-                             (hipStream_t)stream);
-    return enqueue_critic(d, b, epsilon, &adv, &f, (hipStream_t)stream);
+    return enqueue_grad(grad_only(MARLNAV_NETWORK_CRITIC, epsilon, 0.0, 0, nullptr, nullptr), d,
+                        b, stream);
 }

@@ -26,7 +26,7 @@
 
 #include "../../include/marlnav.h"
 
-__attribute__((visibility("hidden"))) int marlnav_internal_fail(int code, const char *msg);
+#include "host_util.h"
 
 namespace {
 
@@ -34,7 +34,6 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 
 #include "block_sum.h"
-#include "host_util.h"
 
 // G_t = done_t ? 0 : r_t + gamma * G_{t+1}  (models.py:133-137)
 __global__ void __launch_bounds__(kThreads) returns_kernel(const float *__restrict__ rew,

@@ -733,16 +733,24 @@ class FusedPPO(object):
             setattr(b, f, t.data_ptr())
             setattr(b, "grad_" + f, g.data_ptr())
         d.num_parallel, d.num_steps = P, T
-        size = self._lib.marlnav_ppo_diag_work_size if diag else self._lib.marlnav_ppo_work_size
-        need = int(size(ctypes.byref(d)))
+        self._grow_work(diag)
+        loss = torch.empty((), dtype=_F64, device=self.device)
+        b.loss = loss.data_ptr()
+        return loss
+
+    def _grow_work(self, diag=False, need=None):
+        """Bind a workspace of ``need`` doubles (the answer of a phase's
+        work-size call; None: what one update of the bound dims needs, with
+        ``diag`` the diagnostic variant's), grown where it is too small."""
+        if need is None:
+            size = self._lib.marlnav_ppo_diag_work_size if diag else self._lib.marlnav_ppo_work_size
+            need = size(ctypes.byref(self._dims))
+        need = int(need)
         if need < 0:
             abi.check(need, self._lib)
         if self._work is None or self._work.numel() < need:
             self._work = torch.empty(need, dtype=_F64, device=self.device)
-        b.work = self._work.data_ptr()
-        loss = torch.empty((), dtype=_F64, device=self.device)
-        b.loss = loss.data_ptr()
-        return loss
+        self._bufs.work = self._work.data_ptr()
 
     def actor_loss_grad(self, buffer, lo, hi, diag_out=None):
         """Actor loss (0-d float64 device tensor) of steps ``lo..hi`` of
@@ -787,15 +795,8 @@ class FusedPPO(object):
         list, the list uploaded as an int32 device table; -> (loss, table)."""
         steps = check_steps(steps, len(buffer))
         loss = self._bind(buffer, 0, len(buffer), network, diag)
-        d, b = self._dims, self._bufs
-        d.num_steps = len(steps)
-        size = self._lib.marlnav_ppo_diag_work_size if diag else self._lib.marlnav_ppo_work_size
-        need = int(size(ctypes.byref(d)))
-        if need < 0:
-            abi.check(need, self._lib)
-        if self._work.numel() < need:
-            self._work = torch.empty(need, dtype=_F64, device=self.device)
-        b.work = self._work.data_ptr()
+        self._dims.num_steps = len(steps)
+        self._grow_work(diag)
         table = torch.tensor(steps, dtype=torch.int32).to(self.device)
         return loss, table
 
@@ -836,18 +837,17 @@ class FusedPPO(object):
         ``train_phase(shuffle=...)`` enqueues per minibatch. ``adam``: a
         ``FusedAdam`` over exactly the six actor parameters in order.
         Returns the loss."""
-        if not (isinstance(adam, FusedAdam) and adam.covers(self._network_params("actor"))):
-            raise ValueError("adam: need a FusedAdam over exactly the actor's parameters in order")
-        loss = self.actor_loss_grad_steps(buffer, steps)
-        adam.step(max_grad_norm=max_grad_norm, norm_out=norm_out)
-        return loss
+        return self._update_steps("actor", buffer, steps, adam, max_grad_norm, norm_out)
 
     def critic_update_steps(self, buffer, steps, adam, max_grad_norm=None, norm_out=None):
         """As ``actor_update_steps``, for the critic."""
-        if not (isinstance(adam, FusedAdam) and adam.covers(self._network_params("critic"))):
-            raise ValueError("adam: need a FusedAdam over exactly the critic's parameters in "
+        return self._update_steps("critic", buffer, steps, adam, max_grad_norm, norm_out)
+
+    def _update_steps(self, network, buffer, steps, adam, max_grad_norm, norm_out):
+        if not (isinstance(adam, FusedAdam) and adam.covers(self._network_params(network))):
+            raise ValueError(f"adam: need a FusedAdam over exactly the {network}'s parameters in "
                              "order")
-        loss = self.critic_loss_grad_steps(buffer, steps)
+        loss = getattr(self, network + "_loss_grad_steps")(buffer, steps)
         adam.step(max_grad_norm=max_grad_norm, norm_out=norm_out)
         return loss
 
@@ -868,40 +868,31 @@ class FusedPPO(object):
         clipped by its global L2 norm before the step, as
         ``adam.step(max_grad_norm=..., norm_out=...)`` does it
         (``marlnav_ppo_actor_update_clipped``, five launches)."""
-        loss = self._bind(buffer, lo, hi)
-        ad, ab = adam._bind()
-        if max_grad_norm is None:
-            if norm_out is not None:
-                raise ValueError("norm_out needs max_grad_norm (inf records the norm only)")
-            abi.check(self._lib.marlnav_ppo_actor_update_mode(
-                ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon, self.ent_const,
-                ctypes.byref(ad), ctypes.byref(ab), self._mode, _stream(self.device)), self._lib)
-            return loss
-        g, work, out = adam._clip_args(max_grad_norm, norm_out)
-        abi.check(self._lib.marlnav_ppo_actor_update_clipped(
-            ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon, self.ent_const,
-            ctypes.byref(ad), ctypes.byref(ab), self._mode, g, work, out,
-            _stream(self.device)), self._lib)
-        return loss
+        return self._update("actor", buffer, lo, hi, adam, max_grad_norm, norm_out)
 
     def critic_update(self, buffer, lo, hi, adam, max_grad_norm=None, norm_out=None):
         """``critic_loss_grad`` then ``adam.step()`` as one C call
         (``marlnav_ppo_critic_update``); ``adam`` over the four critic
         parameters. As ``actor_update``, ``max_grad_norm`` included
         (``marlnav_ppo_critic_update_clipped``)."""
-        loss = self._bind(buffer, lo, hi, 'critic')
+        return self._update("critic", buffer, lo, hi, adam, max_grad_norm, norm_out)
+
+    def _update(self, network, buffer, lo, hi, adam, max_grad_norm, norm_out):
+        """``actor_update`` / ``critic_update``: the network's one-call update,
+        its ``_clipped`` form with ``max_grad_norm``; the critic's take no
+        ``ent_const`` and no advantage mode."""
+        loss = self._bind(buffer, lo, hi, network)
         ad, ab = adam._bind()
+        clip = adam._clip_args(max_grad_norm, norm_out)
+        actor = network == "actor"
+        entry = f"marlnav_ppo_{network}_update_clipped"
         if max_grad_norm is None:
-            if norm_out is not None:
-                raise ValueError("norm_out needs max_grad_norm (inf records the norm only)")
-            abi.check(self._lib.marlnav_ppo_critic_update(
-                ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon,
-                ctypes.byref(ad), ctypes.byref(ab), _stream(self.device)), self._lib)
-            return loss
-        g, work, out = adam._clip_args(max_grad_norm, norm_out)
-        abi.check(self._lib.marlnav_ppo_critic_update_clipped(
+            entry = "marlnav_ppo_actor_update_mode" if actor else "marlnav_ppo_critic_update"
+            clip = ()
+        abi.check(getattr(self._lib, entry)(
             ctypes.byref(self._dims), ctypes.byref(self._bufs), self.epsilon,
-            ctypes.byref(ad), ctypes.byref(ab), g, work, out, _stream(self.device)), self._lib)
+            *((self.ent_const,) if actor else ()), ctypes.byref(ad), ctypes.byref(ab),
+            *((self._mode,) if actor else ()), *clip, _stream(self.device)), self._lib)
         return loss
 
 
@@ -1018,7 +1009,14 @@ class FusedAdam(object):
         """-> (max_norm, norm_work pointer, norm_out pointer or None) of a
         clipped call; the scratch is allocated at the first one. ``norm_out``:
         None or a contiguous float64 tensor of ``count`` elements on the
-        device. The value is checked here and again by the library."""
+        device. The value is checked here and again by the library.
+        ``max_grad_norm`` None, no clip: ``(abi.MAX_NORM_NONE, None, None)``,
+        and a ``norm_out`` is a ValueError."""
+        if max_grad_norm is None:
+            if norm_out is not None:
+                raise ValueError(f"{what} needs max_grad_norm (inf records the "
+                                 f"norm{'s' if count != 1 else ''} only)")
+            return abi.MAX_NORM_NONE, None, None
         g = check_max_grad_norm(max_grad_norm)
         if self._norm_work is None:
             need = int(self._lib.marlnav_grad_norm_work_size(ctypes.byref(self._dims)))
@@ -1048,13 +1046,11 @@ class FusedAdam(object):
         ``marlnav_adam_step_clipped`` (three launches), nothing synchronises;
         the value travels as a launch argument, so a captured graph keeps it."""
         d, b = self._bind()
+        g, work, out = self._clip_args(max_grad_norm, norm_out)
         if max_grad_norm is None:
-            if norm_out is not None:
-                raise ValueError("norm_out needs max_grad_norm (inf records the norm only)")
             abi.check(self._lib.marlnav_adam_step(ctypes.byref(d), ctypes.byref(b),
                                                   _stream(self.device)), self._lib)
             return
-        g, work, out = self._clip_args(max_grad_norm, norm_out)
         abi.check(self._lib.marlnav_adam_step_clipped(ctypes.byref(d), ctypes.byref(b), g, work,
                                                       out, _stream(self.device)), self._lib)
 
@@ -1181,26 +1177,36 @@ def _train_steps(ppo, update_steps, network, buffer, optimizer, num_epochs, batc
     if not (isinstance(optimizer, FusedAdam) and optimizer.covers(network)):
         raise ValueError("steps_table needs a FusedAdam over exactly this network's parameters "
                          "in order")
-    if max_grad_norm is None:
-        if norm_log is not None:
-            raise ValueError("norm_log needs max_grad_norm (inf records the norms only)")
-    else:
+    _check_norm_log(max_grad_norm, norm_log)
+    _run_updates(ppo, [steps for perm in rows for steps in shuffled_minibatches(perm, batch_size)],
+                 lambda steps, norm: update_steps(buffer, steps, optimizer,
+                                                  max_grad_norm=max_grad_norm, norm_out=norm),
+                 log, norm_log)
+
+
+def _check_norm_log(max_grad_norm, norm_log):
+    if max_grad_norm is not None:
         check_max_grad_norm(max_grad_norm)
-    cells, k = None, 0
-    if norm_log is not None:
-        cells = torch.empty(len(rows) * (len(buffer) // int(batch_size)), dtype=_F64,
-                            device=ppo.device)
-    for perm in rows:
-        for steps in shuffled_minibatches(perm, batch_size):
-            norm = None
-            if cells is not None:
-                norm = cells[k]
-                norm_log.append(norm)
-                k += 1
-            loss = update_steps(buffer, steps, optimizer, max_grad_norm=max_grad_norm,
-                                norm_out=norm)
-            if log is not None:
-                log.append(loss)
+    elif norm_log is not None:
+        raise ValueError("norm_log needs max_grad_norm (inf records the norms only)")
+
+
+def _run_updates(ppo, minibatches, update, log, norm_log):
+    """What both host loops do per minibatch: ``update(minibatch, norm)`` ->
+    loss, ``norm`` the update's cell of one allocation (appended to the list
+    ``norm_log``) or None where the norms are not logged; the loss, left on
+    the device, is appended to ``log``."""
+    cells = None
+    if norm_log is not None:                # one allocation, an element per update
+        cells = torch.empty(len(minibatches), dtype=_F64, device=ppo.device)
+    for k, minibatch in enumerate(minibatches):
+        norm = None
+        if cells is not None:
+            norm = cells[k]
+            norm_log.append(norm)
+        loss = update(minibatch, norm)
+        if log is not None:
+            log.append(loss)
 
 
 def _train(ppo, loss_grad, update, network, buffer, optimizer, num_epochs, batch_size, log,
@@ -1210,35 +1216,20 @@ def _train(ppo, loss_grad, update, network, buffer, optimizer, num_epochs, batch
     # a FusedAdam over exactly this network's parameters: one C call per
     # minibatch; any other optimiser: the two calls
     one_call = isinstance(optimizer, FusedAdam) and optimizer.covers(network)
-    if max_grad_norm is None:
-        if norm_log is not None:
-            raise ValueError("norm_log needs max_grad_norm (inf records the norms only)")
-    else:
-        check_max_grad_norm(max_grad_norm)
-        if not one_call:
-            raise ValueError("max_grad_norm needs a FusedAdam over exactly this network's "
-                             "parameters in order: the clipping is part of its step (clip any "
-                             "other optimiser's gradients yourself between loss_grad and step)")
-    cells, k = None, 0
-    if norm_log is not None:                # one allocation, an element per update
-        cells = torch.empty(int(num_epochs) * len(bounds), dtype=_F64, device=ppo.device)
-    for _ in range(int(num_epochs)):
-        for lo, hi in bounds:
-            if max_grad_norm is not None:
-                norm = None
-                if cells is not None:
-                    norm = cells[k]
-                    norm_log.append(norm)
-                    k += 1
-                loss = update(buffer, lo, hi, optimizer, max_grad_norm=max_grad_norm,
-                              norm_out=norm)
-            elif one_call:
-                loss = update(buffer, lo, hi, optimizer)
-            else:
-                loss = loss_grad(buffer, lo, hi)
-                optimizer.step()
-            if log is not None:
-                log.append(loss)
+    _check_norm_log(max_grad_norm, norm_log)
+    if max_grad_norm is not None and not one_call:
+        raise ValueError("max_grad_norm needs a FusedAdam over exactly this network's "
+                         "parameters in order: the clipping is part of its step (clip any "
+                         "other optimiser's gradients yourself between loss_grad and step)")
+
+    def one(lo_hi, norm):
+        if one_call:
+            return update(buffer, *lo_hi, optimizer, max_grad_norm=max_grad_norm, norm_out=norm)
+        loss = loss_grad(buffer, *lo_hi)
+        optimizer.step()
+        return loss
+
+    _run_updates(ppo, bounds * int(num_epochs), one, log, norm_log)
 
 
 def train_actor(ppo, buffer, optimizer, num_epochs, batch_size, log=None, max_grad_norm=None,

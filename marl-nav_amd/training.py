@@ -302,83 +302,42 @@ def train_phase(ppo, buffer, adam, network, num_epochs, batch_size, out=None, ma
     ppo._bind(buffer, 0, len(buffer), name)
     d, b = ppo._dims, ppo._bufs
     if shuffle is not None:
-        return _shuffled_phase(ppo, adam, name, nets[network], int(batch_size), E, B, out,
-                               max_grad_norm, norm_out, monitored, target_kl, diag_out, stop_out,
-                               shuffle)
-    arr = (ctypes.c_int64 * (2 * B))(*[x for b in bounds for x in b])
-    size = lib.marlnav_ppo_train_diag_work_size if monitored else lib.marlnav_ppo_train_work_size
-    need = int(size(ctypes.byref(d), arr, B))
-    if need < 0:
-        abi.check(need, lib)
-    if ppo._work.numel() < need:
-        ppo._work = torch.empty(need, dtype=_F64, device=dev)
-    b.work = ppo._work.data_ptr()
-    ad, ab = adam._bind()
-    if monitored:
-        if max_grad_norm is None:
-            if norm_out is not None:
-                raise ValueError("norm_out needs max_grad_norm (inf records the norms only)")
-            g, work, norms = abi.MAX_NORM_NONE, None, None
-        else:
-            g, work, norms = adam._clip_args(max_grad_norm, norm_out, count=E * B)
-        abi.check(lib.marlnav_ppo_train_phase_monitored(
-            nets[network], ctypes.byref(d), ctypes.byref(b), arr, B, E, ppo.epsilon,
-            ppo.ent_const, ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(), ppo._mode, g, work,
-            norms, target_kl, diag_out.data_ptr(), stop_out.data_ptr(),
-            torch._C._cuda_getCurrentRawStream(dev.index)), lib)
-        ppo.last_diag, ppo.last_stop = diag_out, stop_out
-        return out
-    if max_grad_norm is None:
-        if norm_out is not None:
-            raise ValueError("norm_out needs max_grad_norm (inf records the norms only)")
-        abi.check(lib.marlnav_ppo_train_phase_mode(
-            nets[network], ctypes.byref(d), ctypes.byref(b), arr, B, E, ppo.epsilon,
-            ppo.ent_const, ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(), ppo._mode,
-            torch._C._cuda_getCurrentRawStream(dev.index)), lib)
-        return out
-    g, work, norms = adam._clip_args(max_grad_norm, norm_out, count=E * B)
-    abi.check(lib.marlnav_ppo_train_phase_clipped(
-        nets[network], ctypes.byref(d), ctypes.byref(b), arr, B, E, ppo.epsilon, ppo.ent_const,
-        ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(), ppo._mode, g, work, norms,
-        torch._C._cuda_getCurrentRawStream(dev.index)), lib)
-    return out
-
-
-def _shuffled_phase(ppo, adam, name, network, batch_size, E, B, out, max_grad_norm, norm_out,
-                    monitored, target_kl, diag_out, stop_out, seed):
-    """``train_phase(shuffle=seed)`` behind its checks: ``ppo``'s structs are
-    bound to the whole buffer."""
-    lib, dev = ppo._lib, ppo.device
-    d, b = ppo._dims, ppo._bufs
-    L = int(d.num_steps)
-    need = int(lib.marlnav_ppo_train_shuffled_work_size(ctypes.byref(d), batch_size,
-                                                        1 if monitored else 0))
-    if need < 0:
-        abi.check(need, lib)
-    if ppo._work.numel() < need:
-        ppo._work = torch.empty(need, dtype=_F64, device=dev)
-    b.work = ppo._work.data_ptr()
-    # the call counter and the table live on ppo: a captured graph keeps their pointers
-    if name not in ppo._shuffle_counter:
-        ppo._shuffle_counter[name] = torch.zeros(1, dtype=torch.int64, device=dev)
-    counter = ppo._shuffle_counter[name]
-    table = ppo.last_steps.get(name)
-    if table is None or tuple(table.shape) != (E, L):
-        table = torch.zeros(E, L, dtype=torch.int32, device=dev)
-    ppo.last_steps[name] = table
-    ad, ab = adam._bind()
-    if max_grad_norm is None:
-        if norm_out is not None:
-            raise ValueError("norm_out needs max_grad_norm (inf records the norms only)")
-        g, work, norms = abi.MAX_NORM_NONE, None, None
+        schedule = (int(batch_size), E)
+        need = lib.marlnav_ppo_train_shuffled_work_size(ctypes.byref(d), int(batch_size),
+                                                        1 if monitored else 0)
     else:
-        g, work, norms = adam._clip_args(max_grad_norm, norm_out, count=E * B)
-    abi.check(lib.marlnav_ppo_train_phase_shuffled(
-        network, ctypes.byref(d), ctypes.byref(b), batch_size, E, ppo.epsilon, ppo.ent_const,
-        ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(), ppo._mode, g, work, norms,
-        target_kl if monitored else 0.0, diag_out.data_ptr() if monitored else None,
-        stop_out.data_ptr() if monitored else None, seed & 0xFFFFFFFFFFFFFFFF,
-        counter.data_ptr(), table.data_ptr(), torch._C._cuda_getCurrentRawStream(dev.index)), lib)
+        schedule = ((ctypes.c_int64 * (2 * B))(*[x for lo_hi in bounds for x in lo_hi]), B, E)
+        size = (lib.marlnav_ppo_train_diag_work_size if monitored
+                else lib.marlnav_ppo_train_work_size)
+        need = size(ctypes.byref(d), *schedule[:2])
+    ppo._grow_work(need=need)
+    if shuffle is not None:
+        # the call counter and the table live on ppo: a captured graph keeps their pointers
+        L = int(d.num_steps)
+        if name not in ppo._shuffle_counter:
+            ppo._shuffle_counter[name] = torch.zeros(1, dtype=torch.int64, device=dev)
+        table = ppo.last_steps.get(name)
+        if table is None or tuple(table.shape) != (E, L):
+            table = torch.zeros(E, L, dtype=torch.int32, device=dev)
+        ppo.last_steps[name] = table
+        draw = (shuffle & 0xFFFFFFFFFFFFFFFF, ppo._shuffle_counter[name].data_ptr(),
+                table.data_ptr())
+    ad, ab = adam._bind()
+    clip = adam._clip_args(max_grad_norm, norm_out, count=E * B)
+    monitor = ((target_kl, diag_out.data_ptr(), stop_out.data_ptr()) if monitored
+               else (0.0, None, None))
+    head = (nets[network], ctypes.byref(d), ctypes.byref(b), *schedule, ppo.epsilon,
+            ppo.ent_const, ctypes.byref(ad), ctypes.byref(ab), out.data_ptr(), ppo._mode)
+    stream = torch._C._cuda_getCurrentRawStream(dev.index)
+    if shuffle is not None:
+        rc = lib.marlnav_ppo_train_phase_shuffled(*head, *clip, *monitor, *draw, stream)
+    elif monitored:
+        rc = lib.marlnav_ppo_train_phase_monitored(*head, *clip, *monitor, stream)
+    elif max_grad_norm is not None:
+        rc = lib.marlnav_ppo_train_phase_clipped(*head, *clip, stream)
+    else:
+        rc = lib.marlnav_ppo_train_phase_mode(*head, stream)
+    abi.check(rc, lib)
     if monitored:
         ppo.last_diag, ppo.last_stop = diag_out, stop_out
     return out
