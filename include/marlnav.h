@@ -294,9 +294,10 @@ int marlnav_critic_values(const MarlnavPolicyDims *dims, const MarlnavPolicyBuff
  * being step t, plus what the call needs beside them. Contiguous; fp32 unless
  * noted. Rows may start at any offset the entry's own type allows (a row of
  * `actions` is always 8-byte aligned, as marlnav_step needs; where a row of
- * `actions` is not 16-byte aligned that step runs the generic wave kernel,
- * and where a row of `obs` is not, that policy launch loads narrower: both
- * bit-identical to the aligned paths). */
+ * `actions` is not 16-byte aligned that step runs the env-block or the
+ * generic wave kernel, which read it in 8-byte pairs, and where a row of
+ * `obs` is not, that policy launch loads narrower: both bit-identical to
+ * the aligned paths). */
 typedef struct MarlnavRolloutBuffers {
     float *obs;                /* (T, P, A, D) normalised observations the policy
                                   read at step t (models.py:110, :113, :124)     */

@@ -964,7 +964,9 @@ __device__ __forceinline__ float bond_term(float d, const MarlnavParams &pr, boo
 // The per-agent reward of _rews_and_terms (environment.py:184-269) for one
 // row, from its target bearing/distance, risk and collision flags, the count
 // of others in the distance band and the torch-order sum of bond terms.
-template <int A, bool FAST, bool REFC>
+// TF: the kTermsFastFlag test as a trait, -1 tested at run time, 1 compiled
+// in (the env-block kernel's BlockFixed::terms_fast).
+template <int A, bool FAST, bool REFC, int TF = -1>
 __device__ __forceinline__ RowOut row_reward(float ta, float td, bool risk_any, bool col_any,
                                              float band, float bond, const MarlnavParams &pr,
                                              bool &ok)
@@ -972,7 +974,7 @@ __device__ __forceinline__ RowOut row_reward(float ta, float td, bool risk_any, 
     const float head = fabsf(ta) < pr.max_angle_diff ? 1.0f : 0.0f;
     const float bandc = band < pr.max_at_prop_d ? band : pr.max_at_prop_d;
     float dsc, soft;
-    if (FAST && (pr.flags & kTermsFastFlag)) {
+    if (FAST && (TF < 0 ? (pr.flags & kTermsFastFlag) != 0 : TF > 0)) {
         // exact: the host set kTermsFastFlag only for parameters inside the
         // div_c / recip_fast guards (terms_fast_params), and FAST coordinates
         // bound every distance (coord_ok), so every operand stays in range
@@ -1012,7 +1014,7 @@ __device__ __forceinline__ RowOut row_reward(float ta, float td, bool risk_any, 
 // max_at_prop_d == 2 (environment.py:62, 66): (d - ideal) / 1 is d - ideal and
 // band / 2 is band * 0.5 exactly, so those two divisions are dropped (a
 // separate instance, chosen per launch by the caller).
-template <int A, int O, bool TERMS, bool FAST, bool REFC = false>
+template <int A, int O, bool TERMS, bool FAST, bool REFC = false, int TF = -1>
 __device__ __forceinline__ RowOut observe_row_own(const float *__restrict__ sts,
                                                   const float *__restrict__ obe,
                                                   const float *__restrict__ tge, int a,
@@ -1070,12 +1072,12 @@ __device__ __forceinline__ RowOut observe_row_own(const float *__restrict__ sts,
         if (TERMS) {
             const float *agd = row + 2 + 2 * O + (A - 1);
             float bond;
-            if (pr.flags & kTermsFastFlag)
+            if (TF < 0 ? (pr.flags & kTermsFastFlag) != 0 : TF > 0)
                 bond = torch_row_sum_r<A - 1>(agd, [&](float d) { return bond_term<true, REFC>(d, pr, ok); });
             else
                 bond = torch_row_sum_r<A - 1>(agd, [&](float d) { return bond_term<false>(d, pr, ok); });
-            out = row_reward<A, FAST, REFC>(pg[0], pd[0], ob_risk || ag_risk, ob_col || ag_col, band,
-                                            bond, pr, ok);
+            out = row_reward<A, FAST, REFC, TF>(pg[0], pd[0], ob_risk || ag_risk, ob_col || ag_col,
+                                                band, bond, pr, ok);
         }
         return out;
     }

@@ -132,13 +132,25 @@ __device__ __forceinline__ void glds_span(const void *src, float *dst, unsigned 
 // reason to - the pair is defined by the asm and next used by vm_landed() -
 // and today no instantiation does; after a compiler or flag change re-check
 // `make asm`: in every block_kernel, no instruction between
-// global_load_dwordx2 v[N:N+1] and the s_waitcnt vmcnt(n) switch may name vN
-// or vN+1. tests/test_block_stage_gpu.py fails on stale actions.
+// global_load_dwordx2 v[N:N+1] and the s_waitcnt vmcnt(n) switch (the fixed
+// instantiations: the per-wave s_waitcnt of block_wait_actions) may name vN
+// or vN+1. tests/test_block_stage_gpu.py and tests/test_block_prologue_gpu.py
+// fail on stale actions.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 global_load_x2_raw(const float *p)
 {
     f32x2 v;
     asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(v) : "v"(p) : "memory");
+    return v;
+}
+
+// The same load (and the same obligation) from a wave-uniform base in SGPRs
+// and a 32-bit byte offset per lane: no 64-bit address math in VGPRs ahead
+// of the wave's first load.
+__device__ __forceinline__ f32x2 global_load_x2_raw(const float *base, uint32_t off)
+{
+    f32x2 v;
+    asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(v) : "v"(off), "s"(base) : "memory");
     return v;
 }
 
@@ -163,6 +175,14 @@ __device__ __forceinline__ void wait_vmcnt(int n)
     case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
     default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
     }
+}
+
+// ... and for a compile-time n
+template <int N>
+__device__ __forceinline__ void wait_vmcnt()
+{
+    static_assert(N >= 0 && N < 64, "vmcnt is six bits");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // plain copy of n elements (partial tiles)

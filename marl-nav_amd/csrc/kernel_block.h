@@ -37,10 +37,85 @@ struct BlockPlan {
     static_assert(A >= 2 && A <= 16, "one wave per agent");
 };
 
+// The fixed instantiations' staging destinations (only block_kernel's
+// staging of a full block, below, uses these).
+// A glds_span destination as an LDS-address-space pointer: the issue site
+// holds no generic-to-local cast (its null-checked form costs eight SALU
+// ahead of the M0 write), so every instruction's M0 takes one SALU. MASK:
+// a piece of fewer than 64 lanes goes out under a literal exec mask (below)
+// instead of a lane compare, a saved exec and a branch.
+typedef __attribute__((address_space(3))) float LdsF;
+template <bool MASK>
+struct LdsDst {
+    LdsF *p;
+    __device__ __forceinline__ LdsDst operator+(int n) const { return LdsDst{p + n}; }
+};
+
+// One LDS-DMA instruction of B bytes per lane for lanes 0..N-1 only: exec is
+// set to the literal mask, the load issued, exec restored to all lanes.
+// PRECONDITION: the caller runs with all 64 lanes active - exec is restored
+// to -1, not to a saved value. That holds at its only call sites, the
+// staging of a full block of a fixed instantiation behind wave-uniform
+// branches; never call it under a lane predicate. M0 arrives by constraint; the exec write sits
+// between its write and the load (the one wait state LDS-DMA needs after an
+// M0 write).
+template <int N, int B>
+__device__ __forceinline__ void glds_lanes(const char *s, LdsF *d, unsigned voff)
+{
+    static_assert(N > 0 && N < 64 && (B == 4 || B == 16), "a partial piece");
+    const uint32_t m0 = (uint32_t)(uintptr_t)d;
+    if constexpr (B == 16)
+        asm volatile("s_bfm_b64 exec, %2, 0\n\tglobal_load_lds_dwordx4 %0, %1\n\t"
+                     "s_mov_b64 exec, -1" ::"v"(voff), "s"(s), "n"(N), "{m0}"(m0)
+                     : "memory");
+    else
+        asm volatile("s_bfm_b64 exec, %2, 0\n\tglobal_load_lds_dword %0, %1\n\t"
+                     "s_mov_b64 exec, -1" ::"v"(voff), "s"(s), "n"(N), "{m0}"(m0)
+                     : "memory");
+}
+
+// piece K (1 KiB, or the 16-byte remainder) of glds_span below
+template <int NB, int AUX, bool MASK, int K>
+__device__ __forceinline__ void glds_piece(const void *src, LdsDst<MASK> dst, unsigned lane)
+{
+    constexpr int N16 = NB / 16;
+    const char *s = in_sgpr(reinterpret_cast<const char *>(src) + K * 1024);
+    if constexpr ((K + 1) * 64 <= N16)
+        __builtin_amdgcn_global_load_lds(s + lane * 16u, (LdsVoid *)(dst.p + K * 256), 16, 0, AUX);
+    else if constexpr (MASK)
+        glds_lanes<N16 - K * 64, 16>(s, dst.p + K * 256, lane * 16u);
+    else if ((int)lane < N16 - K * 64)
+        __builtin_amdgcn_global_load_lds(s + lane * 16u, (LdsVoid *)(dst.p + K * 256), 16, 0, AUX);
+}
+
+template <int NB, int AUX, bool MASK, int... K>
+__device__ __forceinline__ void glds_pieces(std::integer_sequence<int, K...>, const void *src,
+                                            LdsDst<MASK> dst, unsigned lane)
+{
+    (glds_piece<NB, AUX, MASK, K>(src, dst, lane), ...);
+}
+
+template <int NB, int AUX = 0, bool MASK>
+__device__ __forceinline__ void glds_span(const void *src, LdsDst<MASK> dst, unsigned lane)
+{
+    constexpr int N16 = NB / 16, R4 = (NB % 16) / 4;
+    static_assert(!MASK || AUX == 0, "the masked pieces carry no cache policy");
+    glds_pieces<NB, AUX>(std::make_integer_sequence<int, (N16 + 63) / 64>{}, src, dst, lane);
+    if constexpr (R4 > 0) {
+        const char *s = in_sgpr(reinterpret_cast<const char *>(src) + N16 * 16);
+        if constexpr (MASK)
+            glds_lanes<R4, 4>(s, dst.p + N16 * 4, lane * 4u);
+        else if ((int)lane < R4)
+            __builtin_amdgcn_global_load_lds(s + lane * 4u, (LdsVoid *)(dst.p + N16 * 4), 4, 0,
+                                             AUX);
+    }
+}
+
 // Copy NB bytes of the block's span k into LDS by LDS-DMA from the wave
 // k % A (spans spread over the block's waves).
-template <int NB, int AUX = 0>
-__device__ __forceinline__ void block_glds(int k, int A, int w, const void *src, float *dst,
+// (DST: float *, or LdsDst above)
+template <int NB, int AUX = 0, class DST>
+__device__ __forceinline__ void block_glds(int k, int A, int w, const void *src, DST dst,
                                            unsigned lane)
 {
     if (k % A == w) glds_span<NB, AUX>(src, dst, lane);
@@ -78,8 +153,9 @@ struct BlockSpans {
 // The issue sites of a full block's spans in their per-wave form: wave W's
 // spans (BlockSpans: K[i] % A == W) in table order, behind one test of the
 // wave index, instead of one wave test per span (block_glds).
-template <int A, int O, bool OBS_ONLY, int W>
-__device__ __forceinline__ void block_stage_wave(const StepPtrs &b, int64_t e0, float *lds,
+// (DST: float *, or LdsDst above)
+template <int A, int O, bool OBS_ONLY, int W, class DST>
+__device__ __forceinline__ void block_stage_wave(const StepPtrs &b, int64_t e0, DST lds,
                                                  unsigned lane, bool formation)
 {
     using BP = BlockPlan<A, O>;
@@ -98,9 +174,9 @@ __device__ __forceinline__ void block_stage_wave(const StepPtrs &b, int64_t e0, 
 }
 
 // w: the wave (uniform; the draw wave, w == A, issues nothing)
-template <int A, int O, bool OBS_ONLY, int... W>
+template <int A, int O, bool OBS_ONLY, class DST, int... W>
 __device__ __forceinline__ void block_stage_waves(std::integer_sequence<int, W...>, int w,
-                                                  const StepPtrs &b, int64_t e0, float *lds,
+                                                  const StepPtrs &b, int64_t e0, DST lds,
                                                   unsigned lane, bool formation)
 {
     ((w == W ? block_stage_wave<A, O, OBS_ONLY, W>(b, e0, lds, lane, formation) : (void)0), ...);
@@ -246,16 +322,60 @@ constexpr bool kBlockEarlyOut = O >= 8 || !HELP;
 struct BlockDynamic {
     static constexpr int all_full = -1, write_through = -1, native_overlap = -1,
                          has_formation = -1, no_norm = -1, no_action_scale = -1,
-                         default_bond = -1, has_counters = -1;
+                         default_bond = -1, has_counters = -1, terms_fast = -1;
     static constexpr bool ptrs_early = false;
+    static constexpr int prologue = 0;
+};
+
+// terms_fast: the reward parameters pass terms_fast_params (kTermsFastFlag,
+// device_math.h), so only the short reward-term divisions are compiled.
+// prologue: the straight-line staging prologue, one bit per piece
+// (marlnav_debug.h MARLNAV_PROLOGUE; all on in the product build).
+enum : int {
+    kProActBase = 1,   // own actions: SGPR block base + 32-bit lane offset
+    kProLdsPtr = 2,    // staging destinations as LDS-address-space pointers
+    kProExecMask = 4,  // partial spans under a literal exec mask
+    kProWait = 8,      // the own-action wait count a constant per wave
+    kProDrawW = 16,    // the stage-time draw's obstacle index is the wave index
+    kProTerms = 32,    // terms_fast compiled in
 };
 
 template <bool WT>
 struct BlockFixed {
+    static constexpr int prologue = MARLNAV_PROLOGUE;
     static constexpr int all_full = 1, write_through = WT, native_overlap = 1, has_formation = 1,
-                         no_norm = 1, no_action_scale = 1, default_bond = 1, has_counters = 1;
+                         no_norm = 1, no_action_scale = 1, default_bond = 1, has_counters = 1,
+                         terms_fast = (prologue & kProTerms) ? 1 : -1;
     static constexpr bool ptrs_early = true;
 };
+
+// The staging destination of a block: the generic LDS pointer, or (kProLdsPtr
+// / kProExecMask) an LdsDst over the same base.
+template <int PRO>
+__device__ __forceinline__ auto block_lds_dst(float *lds)
+{
+    if constexpr (PRO & (kProLdsPtr | kProExecMask))
+        return LdsDst<(PRO & kProExecMask) != 0>{(LdsF *)lds};
+    else
+        return lds;
+}
+
+// The fixed instantiations' wait for a wave's own actions: the count is a
+// constant per wave (BlockSpans::after_actions with the formation span), so
+// A - 1 compares on the wave index select the s_waitcnt.
+template <int A, int O, int W = 0>
+__device__ __forceinline__ void block_wait_actions(int w)
+{
+    constexpr int n = BlockSpans<A, O>::after_actions(W, true);
+    if constexpr (W == A - 1) {
+        wait_vmcnt<n>();
+    } else {
+        if (w == W)
+            wait_vmcnt<n>();
+        else
+            block_wait_actions<A, O, W + 1>(w);
+    }
+}
 
 // A pack member V is read as `V < 0 ? <the run-time test> : V > 0`: the
 // condition is a constant, so only the chosen arm is compiled and the
@@ -333,7 +453,11 @@ __global__ void __launch_bounds__(64 * (A + HELP))
     f32x2 act_own = {0.0f, 0.0f};
     if (!OBS_ONLY && full && !hw) {
         const float *pa = h_actions + ((e0 + lane) * A + w) * 2;
-        if constexpr (WS) {
+        if constexpr (WS && (FX::prologue & kProActBase) != 0) {
+            // the block's and the wave's part in SGPRs, the lane's in 32 bits
+            act_own = global_load_x2_raw(in_sgpr(h_actions + e0 * (2 * A) + 2 * w),
+                                         lane * (8u * A));
+        } else if constexpr (WS) {
             act_own = global_load_x2_raw(pa);
         } else {
             __builtin_amdgcn_global_load_lds(pa, (LdsVoid *)actw, 4, 0, 0);
@@ -345,18 +469,19 @@ __global__ void __launch_bounds__(64 * (A + HELP))
     static_assert(BS::NB[0] == R * 20 && BS::NB[1] == E * O * 8 && BS::NB[2] == E * 8 &&
                       BS::NB[3] == E * 4 && BS::NB[4] == E && BS::NB[5] == (5 * A + 2) * 4,
                   "span table and LDS plan agree");
+    const auto ldst = block_lds_dst<FX::prologue>(lds);  // (the generic pointer unless FX says so)
     if (WS && full) {
-        block_stage_waves<A, O, OBS_ONLY>(std::make_integer_sequence<int, A>{}, w, b, e0, lds, lane,
+        block_stage_waves<A, O, OBS_ONLY>(std::make_integer_sequence<int, A>{}, w, b, e0, ldst, lane,
                                           has_form());
     } else if (full) {
-        block_glds<BS::NB[0]>(BS::K[0], A, w, b.states + e0 * (A * 5), st, lane);
-        block_glds<BS::NB[1]>(BS::K[1], A, w, b.obstacles + e0 * (O * 2), lds + BP::OB, lane);
-        block_glds<BS::NB[2]>(BS::K[2], A, w, b.target + e0 * 2, lds + BP::TG, lane);
+        block_glds<BS::NB[0]>(BS::K[0], A, w, b.states + e0 * (A * 5), ldst + BP::ST, lane);
+        block_glds<BS::NB[1]>(BS::K[1], A, w, b.obstacles + e0 * (O * 2), ldst + BP::OB, lane);
+        block_glds<BS::NB[2]>(BS::K[2], A, w, b.target + e0 * 2, ldst + BP::TG, lane);
         if (!OBS_ONLY) {
-            block_glds<BS::NB[3]>(BS::K[3], A, w, b.step_num + e0, lds + BP::SN, lane);
-            block_glds<BS::NB[4]>(BS::K[4], A, w, b.terminates + e0, lds + BP::TM, lane);
+            block_glds<BS::NB[3]>(BS::K[3], A, w, b.step_num + e0, ldst + BP::SN, lane);
+            block_glds<BS::NB[4]>(BS::K[4], A, w, b.terminates + e0, ldst + BP::TM, lane);
             if (has_form())
-                block_glds<BS::NB[5]>(BS::K[5], A, w, b.formation, lds + BP::FORM, lane);
+                block_glds<BS::NB[5]>(BS::K[5], A, w, b.formation, ldst + BP::FORM, lane);
         }
     } else if (!hw) {
         const int nr = ne * A;
@@ -420,7 +545,11 @@ __global__ void __launch_bounds__(64 * (A + HELP))
 #pragma unroll
         for (int k2 = 0; k2 * NT < E * O; ++k2) {
             const int i = tid + k2 * NT;
-            const int l = i % E, j = __builtin_amdgcn_readfirstlane(i / E);
+            // (kProDrawW: E = 64 and NT = 64 A, so i / E is w + k2 A and
+            // i % E the lane: no second read of the wave index)
+            constexpr bool kW = (FX::prologue & kProDrawW) != 0 && E == 64 && NT == 64 * A;
+            const int l = kW ? (int)lane : i % E;
+            const int j = kW ? w + k2 * A : __builtin_amdgcn_readfirstlane(i / E);
             if (((k2 + 1) * NT <= E * O || i < E * O) && l < ne) {
                 float v[2];
                 native_obst_draw(pr.seed, sidx, g0 + l, j, pr.obs_range_x, pr.obs_mean_x,
@@ -434,7 +563,10 @@ __global__ void __launch_bounds__(64 * (A + HELP))
     // remaining staging latency
     float sn = 0.0f, c = 1.0f, a1 = 0.0f;
     if (!OBS_ONLY && !hw) {
-        if (full) {
+        if constexpr (WS && (FX::prologue & kProWait) != 0 && FX::all_full > 0 &&
+                      FX::has_formation > 0) {
+            block_wait_actions<A, O>(w);
+        } else if (full) {
             // span instructions this wave issued after its action load(s)
             // (BlockSpans: the same table as the issue sites above)
             int n = 0;
@@ -549,13 +681,13 @@ __global__ void __launch_bounds__(64 * (A + HELP))
         if (__builtin_expect(fast, 1) &&
             (FX::default_bond < 0 ? pr.bond_sharpness == 1.0f && pr.max_at_prop_d == 2.0f
                                   : FX::default_bond > 0))
-            ro = observe_row_own<A, O, !OBS_ONLY, true, true>(st + 5 * A * l, lds + BP::OB + 2 * O * l,
-                                                              lds + BP::TG + 2 * l, w, ox, oy, dx,
-                                                              dy, rowv, pr, unused);
+            ro = observe_row_own<A, O, !OBS_ONLY, true, true, FX::terms_fast>(
+                st + 5 * A * l, lds + BP::OB + 2 * O * l, lds + BP::TG + 2 * l, w, ox, oy, dx, dy,
+                rowv, pr, unused);
         else if (FX::default_bond <= 0 && __builtin_expect(fast, 1))
-            ro = observe_row_own<A, O, !OBS_ONLY, true>(st + 5 * A * l, lds + BP::OB + 2 * O * l,
-                                                        lds + BP::TG + 2 * l, w, ox, oy, dx, dy,
-                                                        rowv, pr, unused);
+            ro = observe_row_own<A, O, !OBS_ONLY, true, false, FX::terms_fast>(
+                st + 5 * A * l, lds + BP::OB + 2 * O * l, lds + BP::TG + 2 * l, w, ox, oy, dx, dy,
+                rowv, pr, unused);
         else
             ro = observe_row_own<A, O, !OBS_ONLY, false>(st + 5 * A * l, lds + BP::OB + 2 * O * l,
                                                          lds + BP::TG + 2 * l, w, ox, oy, dx, dy,

@@ -98,3 +98,19 @@ typedef __attribute__((address_space(1))) unsigned long long stamp_t;
 #ifndef MARLNAV_AB
 #define MARLNAV_AB 0
 #endif
+
+// The pieces of the fixed env-block instantiations' staging prologue
+// (kernel_block.h BlockFixed::prologue), one bit each, all on in the product
+// build; -DMARLNAV_PROLOGUE=bits builds a library with a subset, so a piece
+// is measured apart (profiles/stage_prologue_ab.txt). Every subset is
+// bit-exact.
+//   1   the own-action load from an SGPR base and a 32-bit lane offset
+//   2   staging destinations as LDS-address-space pointers
+//   4   partial spans under a literal exec mask (takes the LDS pointers of
+//       bit 2 with it: the masked instruction's M0 is written from one)
+//   8   the own-action wait count a constant per wave
+//   16  the stage-time draw's obstacle index from the wave index
+//   32  the reward terms' short divisions compiled in (terms_fast)
+#ifndef MARLNAV_PROLOGUE
+#define MARLNAV_PROLOGUE 63
+#endif

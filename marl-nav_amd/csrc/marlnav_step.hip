@@ -445,7 +445,8 @@ const BlockVariant *select_block(const MarlnavDims *d, const MarlnavStepBuffers 
     if (!aligned(b.states, 16) || !aligned(b.obstacles, 16) || !aligned(b.target, 16) ||
         !aligned(b.obs, 16) || (b.states_out && !aligned(b.states_out, 16)))
         return nullptr;
-    if (!obs_only && (!aligned(b.actions, 16) || !aligned(b.step_num, 16) ||
+    // (the actions are read as one 8-byte pair or two dwords per lane)
+    if (!obs_only && (!aligned(b.actions, 8) || !aligned(b.step_num, 16) ||
                       !aligned(b.terminates, 16) || (b.formation && !aligned(b.formation, 16))))
         return nullptr;
     return v;
@@ -544,7 +545,8 @@ bool block_fixed_eligible(const MarlnavDims *d, const MarlnavParams &pr,
     return d->num_parallel % v.E == 0 && !noisy && !b.fresh_states && b.formation &&
            !(pr.flags & (MARLNAV_WRITE_OBS_NORM | MARLNAV_SCALE_ACTIONS)) &&
            pr.bond_sharpness == 1.0f && pr.max_at_prop_d == 2.0f && b.counters &&
-           nblk <= L.waves;
+           nblk <= L.waves &&
+           (BlockFixed<false>::terms_fast < 0 || (pr.flags & kTermsFastFlag) != 0);
 }
 
 }  // namespace
